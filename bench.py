@@ -19,6 +19,14 @@ both sides; the MAX elapsed time over ranks is used.  Rank 0 prints ONE JSON lin
 value = total streamed tokens per second over all N GPUs (= streams / ITL); p50 ITL is reported
 in ``p50_itl_ms``.  Weights are random-init bf16 of the exact Mistral-7B-v0.3 architecture and
 prompts are synthetic (no network): ``data = "synthetic"``.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  ``--dump-outputs DIR`` also writes
+what the last timed step handed to its caller as ``DIR/<name>.npy`` (float32): ``token_ids`` (the token sampled
+for every stream), ``logits`` (the fp32 rows they were drawn from) and ``sequence`` (that token's number in its
+stream), one row per stream in conversation order.  Weights, prompts, sampling seeds and the admission order are
+fixed by the arguments, so two builds can be compared output for output.  ``--full`` is where anything beyond the
+headline figure (further configurations, baselines, comparisons) belongs; today the benchmark has none, so it
+changes nothing.
 """
 from __future__ import annotations
 
@@ -48,7 +56,14 @@ def main():
     ap.add_argument("--stub-step-ms", type=float, default=0.0,
                     help="host-path rehearsal only: paced stub replicas emitting one token per stream every "
                          "STUB_STEP_MS instead of the model (router/bus/SSE/client at N GPUs' token rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (token ids, logits) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure (nothing today: a plain run is the whole "
+                         "benchmark)")
     args = ap.parse_args()
+    if args.dump_outputs and args.stub_step_ms:
+        ap.error("--dump-outputs needs the model (not --stub-step-ms)")
 
     from distributed_sse_for_llm_response_amd.engine import bench_harness
 
@@ -77,12 +92,18 @@ def main():
         res = bench_harness.run_serving_bench(client, model=args.model, device=device, streams=args.streams,
                                               prompt_len=args.prompt_len, steps=args.steps, warmup=args.warmup,
                                               tp=args.tp, use_graphs=not args.no_graph, rank=rank, world=world,
-                                              stub_step_ms=args.stub_step_ms)
+                                              stub_step_ms=args.stub_step_ms, dump=bool(args.dump_outputs))
     else:
         res = bench_harness.run_decode_bench(model=args.model, device=device, streams=args.streams,
                                              prompt_len=args.prompt_len, steps=args.steps, warmup=args.warmup,
                                              tp=args.tp, delivery=args.delivery, use_graphs=not args.no_graph,
-                                             rank=rank, world=world)
+                                             rank=rank, world=world, dump=bool(args.dump_outputs))
+    if args.dump_outputs and res.get("outputs"):  # one replica each (tp > 1: its leader); replicas past the first
+        import numpy as np                        # tag their files with their rank
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in res["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
     elapsed = res["elapsed_s"]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)

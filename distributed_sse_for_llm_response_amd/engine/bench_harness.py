@@ -120,8 +120,30 @@ def _build_runner(model: str, device, streams: int, prompt_len: int, total_steps
     return cfg, runner
 
 
+DUMP_LOGIT_BYTES = 48 << 20  # bench.py --dump-outputs: larger logits are dumped as a fixed sample of their columns
+
+
+def snapshot_outputs(r: ModelRunner, row: int, order: list, sequence: list | None = None) -> dict:
+    """What the decode step that wrote token-ring row `row` handed to its caller, for bench.py --dump-outputs (call
+    with the device idle): the sampled token of every stream and the fp32 logits it was drawn from, one row per
+    stream in the order of the slots `order`; `sequence`: the number of that token in its stream.  Float arrays
+    (token ids are exact in float32)."""
+    idx = torch.tensor(order, dtype=torch.long, device=r.device)
+    logits = r.logits.index_select(0, idx).float().cpu().numpy()
+    out = {"token_ids": r.ring[row].index_select(0, idx).cpu().numpy().astype(np.float32)}
+    if logits.nbytes > DUMP_LOGIT_BYTES:
+        keep = DUMP_LOGIT_BYTES // (4 * logits.shape[0])
+        cols = np.sort(np.random.default_rng(0).choice(logits.shape[1], size=keep, replace=False))
+        out["logits_columns"] = cols.astype(np.float64)
+        logits = np.ascontiguousarray(logits[:, cols])
+    out["logits"] = logits
+    if sequence is not None:
+        out["sequence"] = np.asarray(sequence, dtype=np.float32)
+    return out
+
+
 def run_decode_bench(model="mistral-7b-v0.3", device=None, streams=64, prompt_len=512, steps=64, warmup=8, tp=1,
-                     delivery="frame", use_graphs=True, rank=0, world=1, seed=0):
+                     delivery="frame", use_graphs=True, rank=0, world=1, seed=0, dump=False):
     device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
     total = steps + warmup
     cfg, r = _build_runner(model, device, streams, prompt_len, total, tp, use_graphs, rank, world)
@@ -192,8 +214,11 @@ def run_decode_bench(model="mistral-7b-v0.3", device=None, streams=64, prompt_le
     _sync(device, world)
     elapsed = time.perf_counter() - t0
     itl = np.diff(np.array(deliver_ts)) * 1000.0 if len(deliver_ts) > 1 else np.array([elapsed * 1000.0])
-    return {"elapsed_s": elapsed, "p50_itl_ms": float(np.percentile(itl, 50)),
-            "p99_itl_ms": float(np.percentile(itl, 99)), "frames_bytes": frames_bytes, "model": cfg.name}
+    res = {"elapsed_s": elapsed, "p50_itl_ms": float(np.percentile(itl, 50)),
+           "p99_itl_ms": float(np.percentile(itl, 99)), "frames_bytes": frames_bytes, "model": cfg.name}
+    if dump and steps > 0:
+        res["outputs"] = snapshot_outputs(r, (head - 1) % RING_SIZE, list(range(streams)), [total + 1] * streams)
+    return res
 
 
 def spawn_client():
@@ -213,7 +238,7 @@ def spawn_client():
 
 
 def run_serving_bench(client, model="mistral-7b-v0.3", device=None, streams=64, prompt_len=512, steps=64, warmup=8,
-                      tp=1, use_graphs=True, rank=0, world=1, seed=0, stub_step_ms=0.0):
+                      tp=1, use_graphs=True, rank=0, world=1, seed=0, stub_step_ms=0.0, dump=False):
     """Full serving path: `streams` real POST /chat SSE connections per engine replica (one client process on
     rank 0) -> native runtime + data-parallel router on rank 0 -> shared-memory ring -> this rank's LLMEngine
     (scheduler, hipGraph decode, token-ring drain) -> ring -> router -> bus -> epoll writers -> sockets.
@@ -298,8 +323,16 @@ def run_serving_bench(client, model="mistral-7b-v0.3", device=None, streams=64, 
             chan.publish_tokens([e.conversation_id for e in events], [e.token_id for e in events],
                                 [e.sequence for e in events], [e.done for e in events], 0, [e.text for e in events])
 
-    def pump(block_ms=0):
-        for req in chan.poll_requests(1024, block_ms):
+    def admit_all():
+        # every request of this replica is queued before its first step, in conversation order (not in the order
+        # the sockets happened to connect): slots, sampling seeds and prefill passes, and with them every stream's
+        # tokens, are then the same from run to run
+        reqs, t_wait = [], time.time()
+        while len(reqs) < streams:
+            reqs += chan.poll_requests(1024, 20)
+            if time.time() - t_wait > 900:
+                raise RuntimeError(f"bench: only {len(reqs)} of {streams} requests arrived")
+        for req in sorted(reqs, key=lambda q: (len(q["conversation_id"]), q["conversation_id"])):
             p = SamplingParams(temperature=1.0, top_p=1.0, max_tokens=req["max_tokens"], ignore_eos=True)
             drv.add(req["conversation_id"], prompt_for_request(tok, req), p, req["arrival_ns"])
 
@@ -319,10 +352,9 @@ def run_serving_bench(client, model="mistral-7b-v0.3", device=None, streams=64, 
     boost = getattr(engine, "mixed_boost_steps", None)
     if boost is not None:
         engine.mixed_boost_steps = -1
+    admit_all()
     while sum(1 for s in engine.slots if s is not None and s.state == "decode") < streams:
-        pump(20 if not engine.has_work() else 0)
-        if engine.has_work() or drv.plan.adds:
-            publish(step())
+        publish(step())
         if time.time() - t_admit > 900:
             raise RuntimeError("bench: streams did not all start decoding")
     if boost is not None:
@@ -355,6 +387,14 @@ def run_serving_bench(client, model="mistral-7b-v0.3", device=None, streams=64, 
     gc.callbacks.remove(on_gc)
     if live() < streams:
         raise RuntimeError(f"bench: only {live()} of {streams} streams were still decoding at the end of the window")
+    outputs = None
+    if dump and steps > 0 and stub_step_ms <= 0:
+        # the last timed step is the newest one enqueued and the device is idle (sync above): its ring row and the
+        # logits buffer hold what it computed; rows in conversation order
+        by_conv = sorted((s for s in engine.slots if s is not None),
+                         key=lambda s: (len(s.conversation_id), s.conversation_id))
+        outputs = snapshot_outputs(r, (engine.ring_head - 1) % RING_SIZE, [s.slot for s in by_conv],
+                                   [s.base + s.decode_enqueued + 1 for s in by_conv])
     while engine.has_work():
         publish(step())
     drv.stop()
@@ -378,7 +418,8 @@ def run_serving_bench(client, model="mistral-7b-v0.3", device=None, streams=64, 
     return {"elapsed_s": elapsed, "p50_itl_ms": float(np.percentile(itl, 50)),
             "p99_itl_ms": float(np.percentile(itl, 99)), "delivered_in_window": delivered,
             "client_errors": res["errors"][:5], "model": cfg.name, "max_context": prompt_len + 16 + total,
-            "stalls": _stall_report(trace, gc_ms, res["arrivals"], t0_ns, t1_ns) if rank == 0 else {}}
+            "stalls": _stall_report(trace, gc_ms, res["arrivals"], t0_ns, t1_ns) if rank == 0 else {},
+            "outputs": outputs}
 
 
 def _stall_report(trace, gc_ms, arrivals, t0_ns, t1_ns) -> dict:

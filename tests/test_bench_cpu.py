@@ -29,8 +29,10 @@ def _json_line(out):
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("world", [1, 2])
-def test_bench_contract(world):
+def test_bench_contract(world, tmp_path):
     args = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--streams", "3", "--prompt-len", "24"]
+    if world == 1:  # the same run also writes its last step's outputs (and accepts --full)
+        args += ["--dump-outputs", str(tmp_path / "out"), "--full"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -48,6 +50,17 @@ def test_bench_contract(world):
     assert d["config"]["global_batch"] == 3 * world and d["config"]["parallelism"] == f"dp{world}"
     assert d["value"] > 0 and d["client_errors"] == []
     assert d["tokens_delivered_in_window"] >= 3 * world * 2
+    if world == 1:
+        import numpy as np
+
+        got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+        assert set(got) == {"token_ids.npy", "logits.npy", "sequence.npy"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+        tok, logits = got["token_ids.npy"], got["logits.npy"]
+        assert tok.shape == (3,) and logits.shape[0] == 3 and ((tok >= 0) & (tok < logits.shape[1])).all()
+        # prefill samples token 1; warmup + timed steps and the admission skew follow: the last timed step's
+        # token is at least number 1 + 1 + 3 of every stream
+        assert (got["sequence.npy"] >= 5).all()
 
 
 @pytest.mark.timeout(600)
