@@ -104,6 +104,12 @@ struct SampleParams {
   float2* cand;              // [B, nchunks] (score, index-as-bits) candidates
   int nchunks;               // vocab chunks per row (unfiltered path)
   int v_global;              // full vocabulary (all TP shards); checked build: sampled ids below it
+  // presence / frequency / repetition penalties (sample_penalty_kernel, the history append of the pick / commit
+  // passes); null = off, what every launcher without penalties passes
+  const int* pen_meta;       // [4, pen_slots]: presence | frequency | repetition (float bits) | n_prompt, per slot
+  int* hist;                 // [pen_slots, hist_ld]: word 0 = tokens held, then the prompt and the generated tokens
+  int hist_ld, pen_slots;
+  const int* row_slot;       // [B] slot of logits row b, or null (row b = slot b)
 };
 
 }  // namespace dsse
@@ -131,7 +137,9 @@ hipError_t dsse_sample_pick(int B, int world, const void* cand, const dsse::Samp
 hipError_t dsse_prefill_sample_gather(const void* x, int T, int H, const int* meta, int NS, const int* slot_meta, int Bm,
                                       void* xl, int* smeta, hipStream_t st);
 hipError_t dsse_prefill_sample_commit(const int* meta, int NS, const int* new_ids, int* ids, int Bm, int* ring, int R,
-                                      int* positions, hipStream_t st);
+                                      int* positions, const int* pen_meta, int* hist, int hist_ld, hipStream_t st);
+hipError_t dsse_sample_penalties(int B, float* logits, const dsse::SampleParams* p, hipStream_t st);
+hipError_t dsse_sample_hist_append(int n, const int* new_ids, const dsse::SampleParams* p, hipStream_t st);
 hipError_t dsse_rmsnorm(int mode, int M, float* resid, int H, const void* delta, const void* embed,
                         const int* ids, const void* w, void* y, float eps, const float* part, int nsplit,
                         int vocab, hipStream_t st);

@@ -1050,6 +1050,106 @@ void sample_pick(const Tensor& cand_all, const c10::optional<Tensor>& active, Te
   DSSE_CHECK_HIP(dsse_sample_pick(B, world, cand_all.data_ptr(), &p, cur_stream()));
 }
 
+// ---- presence / frequency / repetition penalties (sampler.hip sample_penalty_kernel, hist_append) ----------------
+// pen_meta: int32 [4 Bm] = [presence | frequency | repetition (float bits) | n_prompt]; hist: int32 [Bm, capacity + 1]
+// = [tokens held | prompt, then generated tokens], both slot-indexed.
+void penalty_state(dsse::SampleParams& p, const Tensor& pen_meta, const Tensor& hist) {
+  check_gpu(pen_meta, "pen_meta");
+  check_gpu(hist, "hist");
+  check_dtype(pen_meta, at::kInt, "pen_meta");
+  check_dtype(hist, at::kInt, "hist");
+  TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous() && hist.size(1) >= 2 && hist.size(1) <= INT32_MAX,
+              "hist must be a contiguous [slots, capacity + 1]");
+  TORCH_CHECK(pen_meta.is_contiguous() && pen_meta.numel() == 4 * hist.size(0), "pen_meta must be [4 x slots]");
+  p.pen_meta = pen_meta.data_ptr<int>();
+  p.hist = hist.data_ptr<int>();
+  p.hist_ld = (int)hist.size(1);
+  p.pen_slots = (int)hist.size(0);
+}
+
+void penalty_rows(dsse::SampleParams& p, const c10::optional<Tensor>& active, const c10::optional<Tensor>& row_slot,
+                  int B) {
+  if (active.has_value()) {
+    check_gpu(*active, "active");
+    check_dtype(*active, at::kInt, "active");
+    TORCH_CHECK(active->numel() >= B, "active too short");
+    p.active = active->data_ptr<int>();
+  }
+  if (row_slot.has_value()) {
+    check_gpu(*row_slot, "row_slot");
+    check_dtype(*row_slot, at::kInt, "row_slot");
+    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
+    p.row_slot = row_slot->data_ptr<int>();
+  } else {
+    TORCH_CHECK(B <= p.pen_slots, "more rows than slots (no row_slot map)");
+  }
+}
+
+// In place on logits [B, V] (row stride >= V), before sample_candidates.
+void sample_penalties(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& pen_meta, const Tensor& hist,
+                      const c10::optional<Tensor>& row_slot, int64_t vocab_offset, int64_t vocab) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");  // (rows may be strided: a column slice of a shard)
+  check_dtype(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
+                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
+  const int B = (int)logits.size(0), V = (int)logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= 32768, "sampler supports V <= 32768 per rank");
+  dsse::SampleParams p{};
+  penalty_state(p, pen_meta, hist);
+  penalty_rows(p, active, row_slot, B);
+  p.ld = (int)logits.stride(0);
+  p.V = V;
+  p.vocab_offset = (int)vocab_offset;
+  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
+  DSSE_CHECK_HIP(dsse_sample_penalties(B, logits.data_ptr<float>(), &p, cur_stream()));
+}
+
+// sample_pick whose picked token also joins hist[b] where slot b has penalties on.
+void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
+                      const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
+                      const c10::optional<Tensor>& positions_inc, const Tensor& pen_meta, const Tensor& hist,
+                      int64_t vocab) {
+  check_gpu(cand_all, "cand_all");
+  check_gpu(next_ids, "next_ids");
+  check_dtype(next_ids, at::kInt, "next_ids");
+  TORCH_CHECK(cand_all.dim() == 4 && cand_all.size(3) == 2, "cand_all must be [world, B, nchunks, 2]");
+  const int world = (int)cand_all.size(0), B = (int)cand_all.size(1);
+  TORCH_CHECK(next_ids.numel() >= B, "next_ids too short");
+  dsse::SampleParams p{};
+  penalty_state(p, pen_meta, hist);
+  penalty_rows(p, active, c10::nullopt, B);
+  p.nchunks = (int)cand_all.size(2);
+  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
+  p.next_ids = next_ids.data_ptr<int>();
+  if (ring.has_value()) {
+    TORCH_CHECK(ring_counter.has_value(), "ring needs ring_counter");
+    check_gpu(*ring, "ring");
+    TORCH_CHECK(ring->dim() == 2 && ring->size(1) >= B, "ring must be [R, >= B]");
+    p.ring = ring->data_ptr<int>();
+    p.ring_counter = ring_counter->data_ptr<int>();
+    p.ring_size = (int)ring->size(0);
+    p.ring_stride = (int)ring->size(1);
+  }
+  if (positions_inc.has_value()) {
+    TORCH_CHECK(positions_inc->numel() >= B, "positions_inc too short");
+    p.positions_inc = positions_inc->data_ptr<int>();
+  }
+  DSSE_CHECK_HIP(dsse_sample_pick(B, world, cand_all.data_ptr(), &p, cur_stream()));
+}
+
+// new_ids[i] joins the history of slot row_slot[i] (else i): the eager first-token path.
+void sample_hist_append(const Tensor& new_ids, const c10::optional<Tensor>& row_slot,
+                        const c10::optional<Tensor>& active, const Tensor& pen_meta, Tensor& hist) {
+  check_gpu(new_ids, "new_ids");
+  check_dtype(new_ids, at::kInt, "new_ids");
+  TORCH_CHECK(new_ids.is_contiguous(), "new_ids must be contiguous");
+  const int n = (int)new_ids.numel();
+  dsse::SampleParams p{};
+  penalty_state(p, pen_meta, hist);
+  penalty_rows(p, active, row_slot, n);
+  DSSE_CHECK_HIP(dsse_sample_hist_append(n, new_ids.data_ptr<int>(), &p, cur_stream()));
+}
+
 // First-token sampling inside the captured prefill / mixed graphs (sampler.hip prefill_sample_*): gather the
 // finishing prompts' last rows + their slots' sampling parameters, then (after the LM head, candidates and pick)
 // commit ids / ring / positions.  meta: int32 [3 NS + 2]; smeta: int32 [7 NS]; slot_meta: the runner's [6 Bm].
@@ -1067,7 +1167,8 @@ void prefill_sample_gather(const Tensor& x, const Tensor& meta, const Tensor& sl
                                             cur_stream()));
 }
 
-void prefill_sample_commit(const Tensor& meta, const Tensor& new_ids, Tensor& ids, Tensor& ring, Tensor& positions) {
+void prefill_sample_commit_impl(const Tensor& meta, const Tensor& new_ids, Tensor& ids, Tensor& ring, Tensor& positions,
+                                const Tensor* pen_meta, const Tensor* hist) {
   for (const Tensor* t : {&meta, &new_ids, (const Tensor*)&ids, (const Tensor*)&ring, (const Tensor*)&positions}) {
     check_gpu(*t, "prefill_sample_commit operand");
     check_dtype(*t, at::kInt, "int32 operand");
@@ -1075,9 +1176,24 @@ void prefill_sample_commit(const Tensor& meta, const Tensor& new_ids, Tensor& id
   const int NS = (int)new_ids.numel(), Bm = (int)ids.numel();
   TORCH_CHECK(NS <= 64 && meta.numel() >= 3 * NS + 2, "meta too short / NS > 64");
   TORCH_CHECK(ring.dim() == 2 && ring.size(1) == Bm && positions.numel() == Bm, "ring must be [R, Bm], positions [Bm]");
+  dsse::SampleParams p{};  // penalty state only (null without)
+  if (hist != nullptr) {
+    penalty_state(p, *pen_meta, *hist);
+    TORCH_CHECK(p.pen_slots == Bm, "hist must have one row per slot of ids");
+  }
   DSSE_CHECK_HIP(dsse_prefill_sample_commit(meta.data_ptr<int>(), NS, new_ids.data_ptr<int>(), ids.data_ptr<int>(), Bm,
                                             ring.data_ptr<int>(), (int)ring.size(0), positions.data_ptr<int>(),
-                                            cur_stream()));
+                                            p.pen_meta, p.hist, p.hist_ld, cur_stream()));
+}
+
+void prefill_sample_commit(const Tensor& meta, const Tensor& new_ids, Tensor& ids, Tensor& ring, Tensor& positions) {
+  prefill_sample_commit_impl(meta, new_ids, ids, ring, positions, nullptr, nullptr);
+}
+
+// prefill_sample_commit whose first tokens also join the history of the slots that have penalties on.
+void prefill_sample_commit_hist(const Tensor& meta, const Tensor& new_ids, Tensor& ids, Tensor& ring, Tensor& positions,
+                                const Tensor& pen_meta, Tensor& hist) {
+  prefill_sample_commit_impl(meta, new_ids, ids, ring, positions, &pen_meta, &hist);
 }
 
 // ---- TP all-reduce over IPC peer buffers (allreduce.hip) ------------------------------------------------------
@@ -1287,6 +1403,14 @@ TORCH_LIBRARY(dsse, m) {
         "Tensor? ring_counter=None, Tensor(c!)? positions_inc=None, int vocab=2147483647) -> ()");
   m.def("prefill_sample_gather(Tensor x, Tensor meta, Tensor slot_meta, Tensor(a!) xl, Tensor(b!) smeta) -> ()");
   m.def("prefill_sample_commit(Tensor meta, Tensor new_ids, Tensor(a!) ids, Tensor(b!) ring, Tensor(c!) positions) -> ()");
+  m.def("sample_penalties(Tensor(a!) logits, Tensor? active, Tensor pen_meta, Tensor hist, Tensor? row_slot=None, "
+        "int vocab_offset=0, int vocab=2147483647) -> ()");
+  m.def("sample_pick_hist(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring, "
+        "Tensor? ring_counter, Tensor(c!)? positions_inc, Tensor pen_meta, Tensor(d!) hist, "
+        "int vocab=2147483647) -> ()");
+  m.def("prefill_sample_commit_hist(Tensor meta, Tensor new_ids, Tensor(a!) ids, Tensor(b!) ring, "
+        "Tensor(c!) positions, Tensor pen_meta, Tensor(d!) hist) -> ()");
+  m.def("sample_hist_append(Tensor new_ids, Tensor? row_slot, Tensor? active, Tensor pen_meta, Tensor(a!) hist) -> ()");
   m.def("ar_alloc(int rows, int H) -> (Tensor, int, int)", &ar_alloc);
   m.def("ar_open(Tensor handle) -> int", &ar_open);
   m.def("ar_close(int ptr, bool opened) -> ()", &ar_close);
@@ -1324,6 +1448,10 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("sample_pick", &sample_pick);
   m.impl("prefill_sample_gather", &prefill_sample_gather);
   m.impl("prefill_sample_commit", &prefill_sample_commit);
+  m.impl("sample_penalties", &sample_penalties);
+  m.impl("sample_pick_hist", &sample_pick_hist);
+  m.impl("prefill_sample_commit_hist", &prefill_sample_commit_hist);
+  m.impl("sample_hist_append", &sample_hist_append);
   m.impl("ar_rmsnorm", &ar_rmsnorm);
   m.impl("ar_gather", &ar_gather);
 }

@@ -166,8 +166,83 @@ __global__ void __launch_bounds__(kSThreads) sample_filtered_kernel(SampleParams
   }
 }
 
+// ---- presence / frequency / repetition penalties -------------------------------------------------------------
+// Per-slot state (slot-indexed like slot_meta, device resident): pen_meta = [presence | frequency | repetition |
+// n_prompt] (host-owned, uploaded with the slot metadata) and the token history hist[slot] = [len | prompt tokens |
+// generated tokens] (the engine uploads a row when it places a penalised sequence in the slot; afterwards the device
+// owns it: the pick / commit passes append every sampled token in stream order, so steps enqueued ahead of the host
+// see the right history).  vLLM's order, before temperature / top-k / top-p and under greedy, with c[v] = the
+// occurrences of v among the generated tokens:
+//   v in prompt or generated: x = x > 0 ? x / r : x * r;   x -= f c[v];   c[v] > 0: x -= p.
+constexpr uint32_t kPenPrompt = 0x80000000u;  // count word: bit 31 = the prompt names the token, bits 0-30 = c[v]
+
+DEV bool penalties_on(const int* __restrict__ pm, int Bm, int slot) {
+  return __int_as_float(pm[slot]) != 0.f || __int_as_float(pm[Bm + slot]) != 0.f ||
+         __int_as_float(pm[2 * Bm + slot]) != 1.f;
+}
+
+// One workgroup per logits row.  A row that is inactive or whose parameters are neutral returns at once (its logits
+// stay bit-identical).  Otherwise: zero a per-vocab count word in LDS, walk the history with LDS atomics (prompt
+// tokens set the flag bit, generated ones count; ids outside this rank's vocab shard are skipped), then rewrite the
+// logits whose word is nonzero, in fp32.  The counts are 32-bit words (V <= kSMaxV: 128 KiB of LDS), so they are
+// exact for every history the int32 row stride can describe (< 2^31 tokens): nothing saturates or wraps into the
+// flag bit.
+__global__ void __launch_bounds__(kSThreads) sample_penalty_kernel(float* __restrict__ logits, SampleParams p) {
+  const int b = blockIdx.x;
+  if (p.active && !p.active[b]) return;
+  const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, p.pen_slots, 0);
+  const int Bm = p.pen_slots;
+  if (!penalties_on(p.pen_meta, Bm, slot)) return;
+  __shared__ uint32_t cnt[kSMaxV];
+  for (int i = threadIdx.x; i < p.V; i += kSThreads) cnt[i] = 0u;
+  __syncthreads();
+  const float pres = __int_as_float(p.pen_meta[slot]), freq = __int_as_float(p.pen_meta[Bm + slot]);
+  const float rep = __int_as_float(p.pen_meta[2 * Bm + slot]);
+  const int n_prompt = p.pen_meta[3 * Bm + slot];
+  const int* h = p.hist + (size_t)slot * p.hist_ld;
+  const int n = min(max(DSSE_IDX(h[0], p.hist_ld, 0), 0), p.hist_ld - 1);
+  for (int j = threadIdx.x; j < n; j += kSThreads) {
+    const int v = DSSE_IDX(h[1 + j], p.v_global, -1) - p.vocab_offset;
+    if ((unsigned)v >= (unsigned)p.V) continue;  // another shard's token (or, checked build, a bad id)
+    if (j < n_prompt) atomicOr(&cnt[v], kPenPrompt);
+    else atomicAdd(&cnt[v], 1u);
+  }
+  __syncthreads();
+  float* row = logits + (size_t)b * p.ld;
+  for (int i = threadIdx.x; i < p.V; i += kSThreads) {
+    const uint32_t w = cnt[i];
+    if (w == 0u) continue;
+    const uint32_t c = w & ~kPenPrompt;
+    float x = row[i];
+    if (rep != 1.f) x = x > 0.f ? x / rep : x * rep;
+    x -= freq * (float)c;
+    if (c > 0u) x -= pres;
+    row[i] = x;
+  }
+}
+
+// The sampled token joins its slot's history (slots with penalties only; a full row drops it: the engine sizes the
+// rows for every token a sequence can sample, max_model_len + 1).
+DEV void hist_append(const int* __restrict__ pen_meta, int Bm, int* __restrict__ hist, int hist_ld, int slot, int id) {
+  if (!penalties_on(pen_meta, Bm, slot)) return;
+  int* h = hist + (size_t)slot * hist_ld;
+  const int n = DSSE_IDX(h[0], hist_ld - 1, -1);
+  if ((unsigned)n >= (unsigned)(hist_ld - 1)) return;
+  h[1 + n] = id;
+  h[0] = n + 1;
+}
+
+// Eager first-token path: new_ids[i] joins the history of slot row_slot[i] (else i).
+__global__ void sample_hist_append_kernel(const int* __restrict__ new_ids, int n, SampleParams p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (p.active && !p.active[i])) return;
+  const int slot = DSSE_IDX(p.row_slot ? p.row_slot[i] : i, p.pen_slots, -1);
+  if (slot < 0) return;
+  hist_append(p.pen_meta, p.pen_slots, p.hist, p.hist_ld, slot, new_ids[i]);
+}
+
 // Merge candidates [world, B, nchunks] (vocab chunks x tensor-parallel shards) and commit the token:
-// next_ids[b], ring[head][b], positions[b] += 1.
+// next_ids[b], ring[head][b], positions[b] += 1 (and, with p.hist, the history append of slot b).
 __global__ void sample_pick_kernel(const float2* __restrict__ cand, int world, int B, SampleParams p) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -183,6 +258,7 @@ __global__ void sample_pick_kernel(const float2* __restrict__ cand, int world, i
   p.next_ids[b] = bidx;
   if (p.ring) p.ring[(size_t)(p.ring_counter[0] % p.ring_size) * p.ring_stride + b] = bidx;
   if (p.positions_inc) p.positions_inc[b] += 1;
+  if (p.hist && b < p.pen_slots) hist_append(p.pen_meta, p.pen_slots, p.hist, p.hist_ld, b, bidx);
 }
 
 // First-token sampling of the prompts a captured prefill / mixed graph finishes (round 6: inside the graph, no torch
@@ -214,10 +290,12 @@ prefill_sample_gather_kernel(const bf16* __restrict__ x, int T, int H, const int
   }
 }
 
-// Commit the picked first tokens: ids[slot], ring[ring_row][slot], positions[slot] = last_pos + 1.
+// Commit the picked first tokens: ids[slot], ring[ring_row][slot], positions[slot] = last_pos + 1 (and, with hist,
+// the history append of the slots that have penalties; pen_meta / hist are [.., Bm] like ids).
 __global__ void prefill_sample_commit_kernel(const int* __restrict__ meta, int NS, const int* __restrict__ new_ids,
                                              int* __restrict__ ids, int Bm, int* __restrict__ ring, int R,
-                                             int* __restrict__ positions) {
+                                             int* __restrict__ positions, const int* __restrict__ pen_meta,
+                                             int* __restrict__ hist, int hist_ld) {
   const int i = threadIdx.x;
   if (i >= NS || i >= meta[3 * NS]) return;
   const int slot = DSSE_IDX(meta[NS + i], Bm, -1);
@@ -226,6 +304,7 @@ __global__ void prefill_sample_commit_kernel(const int* __restrict__ meta, int N
   ids[slot] = new_ids[i];
   ring[(size_t)row * Bm + slot] = new_ids[i];
   positions[slot] = meta[2 * NS + i] + 1;
+  if (hist) hist_append(pen_meta, Bm, hist, hist_ld, slot, new_ids[i]);
 }
 
 }  // namespace dsse
@@ -240,10 +319,30 @@ extern "C" hipError_t dsse_prefill_sample_gather(const void* x, int T, int H, co
 }
 
 extern "C" hipError_t dsse_prefill_sample_commit(const int* meta, int NS, const int* new_ids, int* ids, int Bm,
-                                                 int* ring, int R, int* positions, hipStream_t st) {
-  if (NS <= 0 || NS > 64) return hipErrorInvalidValue;
+                                                 int* ring, int R, int* positions, const int* pen_meta, int* hist,
+                                                 int hist_ld, hipStream_t st) {
+  if (NS <= 0 || NS > 64 || (hist && (!pen_meta || hist_ld < 2))) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dsse::prefill_sample_commit_kernel, dim3(1), dim3(64), 0, st, meta, NS, new_ids, ids, Bm, ring,
-                     R, positions);
+                     R, positions, pen_meta, hist, hist_ld);
+  return hipGetLastError();
+}
+
+// Penalty pass over logits [B, p->ld] in place (p: active, V, ld, vocab_offset, v_global, pen_meta, hist, hist_ld,
+// pen_slots, row_slot).
+extern "C" hipError_t dsse_sample_penalties(int B, float* logits, const dsse::SampleParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (p->V > dsse::kSMaxV || p->V < 1 || p->ld < p->V || !p->pen_meta || !p->hist || p->hist_ld < 2 ||
+      p->pen_slots < 1)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::sample_penalty_kernel, dim3(B), dim3(dsse::kSThreads), 0, st, logits, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t dsse_sample_hist_append(int n, const int* new_ids, const dsse::SampleParams* p,
+                                              hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!p->pen_meta || !p->hist || p->hist_ld < 2 || p->pen_slots < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::sample_hist_append_kernel, dim3((n + 63) / 64), dim3(64), 0, st, new_ids, n, *p);
   return hipGetLastError();
 }
 

@@ -31,6 +31,9 @@ std::string encode_request(const ChatRequest& r) {
   w.u8(r.ignore_eos ? 1 : 0);
   w.u8(r.from_edge ? 1 : 0);
   w.str(r.messages_json);
+  w.f64(r.presence_penalty);
+  w.f64(r.frequency_penalty);
+  w.f64(r.repetition_penalty);
   return w.data();
 }
 
@@ -47,6 +50,9 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   r->ignore_eos = rd.u8() != 0;
   r->from_edge = rd.u8() != 0;
   r->messages_json = rd.str();
+  r->presence_penalty = rd.f64();
+  r->frequency_penalty = rd.f64();
+  r->repetition_penalty = rd.f64();
   return rd.good();
 }
 }  // namespace dpwire

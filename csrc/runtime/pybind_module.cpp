@@ -37,6 +37,9 @@ py::dict request_dict(const ChatRequest& r) {
   d["top_k"] = r.top_k;
   d["seed"] = r.seed;
   d["ignore_eos"] = r.ignore_eos;
+  d["presence_penalty"] = r.presence_penalty;
+  d["frequency_penalty"] = r.frequency_penalty;
+  d["repetition_penalty"] = r.repetition_penalty;
   d["from_edge"] = r.from_edge;
   d["messages"] = r.messages_json;
   return d;

@@ -229,8 +229,27 @@ std::string simple_response(int code, const std::string& body, const std::string
   r += body;
   return r;
 }
+// presence_penalty / frequency_penalty in [-2, 2] and repetition_penalty in (0, 2] of a /chat or
+// /v1/chat/completions body: absent = no penalty; present but not a finite number in range: false with *err -> 400.
+bool parse_penalties(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err) {
+  auto one = [&](const char* k, bool open_lo, double lo, double* out) {
+    auto it = o.find(k);
+    if (it == o.end()) return true;
+    const double v = it->second.kind == JsonValue::kNumber ? it->second.num : NAN;
+    if (!std::isfinite(v) || v > 2 || (open_lo ? v <= lo : v < lo)) {
+      *err = std::string(k) + " must be a number in " + (open_lo ? "(0, 2]" : "[-2, 2]");
+      return false;
+    }
+    *out = v;
+    return true;
+  };
+  return one("presence_penalty", false, -2, &r.presence_penalty) &&
+         one("frequency_penalty", false, -2, &r.frequency_penalty) &&
+         one("repetition_penalty", true, 0, &r.repetition_penalty);
+}
+
 // Optional sampling fields of a /chat body ({message, conversation_id} plus max_tokens, temperature, top_p,
-// top_k, seed, ignore_eos).  Integers must be integral and in range BEFORE any conversion (a double outside the
+// top_k, seed, ignore_eos, and the three penalties above). Integers must be integral and in range BEFORE any conversion (a double outside the
 // target type's range is undefined behaviour to cast): false with *err otherwise -> 400.
 bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err) {
   auto num = [&](const char* k, double dflt) {
@@ -257,6 +276,7 @@ bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, s
     *err = "temperature and top_p must be finite";
     return false;
   }
+  if (!parse_penalties(o, r, err)) return false;
   r.max_tokens = (int)max_tokens;
   r.top_k = (int)top_k;
   r.seed = seed;
@@ -818,6 +838,10 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   r.top_p = top_p;
   r.top_k = (int)top_k;
   r.seed = seed;
+  {
+    std::string pen_err;
+    if (!parse_penalties(o, r, &pen_err)) return bad(400, pen_err);
+  }
   {
     auto ie = o.find("ignore_eos");
     r.ignore_eos = ie != o.end() && ie->second.kind == JsonValue::kBool && ie->second.b;

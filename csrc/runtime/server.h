@@ -85,7 +85,10 @@ struct ChatRequest {
   int top_k = -1;
   int64_t seed = -1;
   bool ignore_eos = false;
-  bool from_edge = false;    // submitted by the edge /chat (a subscriber exists)
+  double presence_penalty = 0;    // [-2, 2]; these three default to "no penalty"
+  double frequency_penalty = 0;   // [-2, 2]
+  double repetition_penalty = 1;  // (0, 2]
+  bool from_edge = false;   // submitted by the edge /chat (a subscriber exists)
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON
   // [{"role":..,"content":..},..]; empty = `message` is a single user turn
   std::string messages_json;

@@ -62,6 +62,14 @@ class SamplingParams:
     max_tokens: int = 256
     seed: int | None = None
     ignore_eos: bool = False
+    # vLLM's token-history penalties, applied in this order before temperature / top-k / top-p (and under greedy);
+    # c[v] = occurrences of v among the generated tokens (sampler.hip sample_penalty_kernel)
+    presence_penalty: float = 0.0    # x[v] -= p where c[v] > 0
+    frequency_penalty: float = 0.0   # x[v] -= f * c[v]
+    repetition_penalty: float = 1.0  # v in the prompt or generated: x[v] = x[v] / r if x[v] > 0 else x[v] * r
+
+    def penalised(self) -> bool:
+        return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
 
 
 FINISH_CODES = {"": 0, "stop": 1, "length": 2, "abort": 3}  # runtime FinishReason (csrc/runtime/json.h)
@@ -293,6 +301,7 @@ class LLMEngine:
         self.drain = _Drain(runner)
         self._rid = itertools.count(1)
         self._dirty_slots: set = set()
+        self._pen_live = False  # the device's penalty block holds a non-neutral slot (then _upload rewrites it)
         self.ring_head = int(runner.ring_counter.item()) if runner.device.type == "cuda" else int(runner.ring_counter[0])
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0}
@@ -432,6 +441,20 @@ class LLMEngine:
             sd = p.seed if p.seed is not None else (s.rid * 2654435761) & 0x7FFFFFFF
             seeds[i, 0] = sd & 0x7FFFFFFF
             seeds[i, 1] = (sd >> 31) & 0x7FFFFFFF
+        # the penalty block [presence | frequency | repetition | n_prompt] (ModelRunner.pen_meta): built and sent only
+        # while a penalised sequence holds a slot, and once more after the last one left (back to neutral).  The
+        # token histories and their lengths are device-owned (ModelRunner.set_history at admission): not touched here
+        pen = None
+        live = [(i, s) for i, s in enumerate(self.slots) if s is not None and s.params.penalised()]
+        if live or self._pen_live:
+            pen = np.zeros(4 * Bm, dtype=np.int32)
+            pf = pen[:3 * Bm].view(np.float32)
+            pf[2 * Bm:] = 1.0
+            for i, s in live:
+                p = s.params
+                pf[i], pf[Bm + i], pf[2 * Bm + i] = p.presence_penalty, p.frequency_penalty, p.repetition_penalty
+                pen[3 * Bm + i] = s.orig_len
+            self._pen_live = bool(live)
         bt_rows = {}
         for i in self._dirty_slots:
             s = self.slots[i]
@@ -448,6 +471,8 @@ class LLMEngine:
                 dst.copy_(src)
 
         put(r.slot_meta, torch.from_numpy(meta))
+        if pen is not None:
+            put(r.pen_meta, torch.from_numpy(pen))
         for i, row in bt_rows.items():
             put(r.block_tables[i], row)
         self._dirty_slots.clear()
@@ -537,6 +562,10 @@ class LLMEngine:
             s.decode_enqueued = 0
             self.slots[s.slot] = s
             self._dirty_slots.add(s.slot)
+            if s.params.penalised():
+                # its history: the prompt as submitted, then (after a preemption) everything it has published
+                # (`prompt` is exactly that); the device appends every token sampled from here on
+                r.set_history(s.slot, s.prompt, s.orig_len)
 
     def _compact(self):
         """Move decoding sequences above the bucket their count needs into lower free / paused slots."""

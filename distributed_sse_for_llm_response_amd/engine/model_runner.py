@@ -225,6 +225,21 @@ class ModelRunner:
         self.top_p = self.slot_meta[3 * Bm:4 * Bm].view(torch.float32)
         self.top_p.fill_(1.0)
         self.seeds = self.slot_meta[4 * Bm:].view(Bm, 2)
+        # presence / frequency / repetition penalties (sampler.hip sample_penalty_kernel): pen_meta = [presence |
+        # frequency | repetition (float32 views) | n_prompt] per slot, host-owned and uploaded like slot_meta;
+        # hist_state[slot] = [tokens held | prompt, then generated tokens], written by the engine when a penalised
+        # sequence takes the slot (set_history) and device-owned afterwards: every sampled token is appended in
+        # stream order by the pick / commit kernels.  max_model_len + 1 tokens hold everything a sequence can sample.
+        self.pen_meta = torch.zeros(4 * Bm, **i32)
+        self.presence = self.pen_meta[:Bm].view(torch.float32)
+        self.frequency = self.pen_meta[Bm:2 * Bm].view(torch.float32)
+        self.repetition = self.pen_meta[2 * Bm:3 * Bm].view(torch.float32)
+        self.repetition.fill_(1.0)
+        self.n_prompt = self.pen_meta[3 * Bm:]
+        self.hist_state = torch.zeros(Bm, max_model_len + 2, **i32)
+        self.hist_len = self.hist_state[:, 0]
+        self.hist = self.hist_state[:, 1:]
+        self.hist_used = False  # a history was ever uploaded (move_slots then moves the rows too)
         self.ring = torch.zeros(RING_SIZE, Bm, **i32)
         self.ring_counter = torch.zeros(1, **i32)
         # ---- decode activations ----
@@ -264,6 +279,9 @@ class ModelRunner:
         self.pf_graphs = {}   # row bucket -> captured prefill graph
         self.pf = None        # static prefill buffers (allocated by capture)
         self.mx_graphs = {}   # decode bucket B -> [(chunk rows C, captured mixed prefill + decode graph)], C ascending
+        # their twins with the penalty pass, captured at the first penalised request (_capture_penalty_graphs)
+        self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs = {}, {}, {}
+        self._graphs_have_pass = False  # capture() ran after penalties were already in use: one set, with the pass
         self.host_trace = None  # a list: host seconds of each graph-replayed mixed step (upload, replay, sampling)
 
     # ------------------------------------------------------------------ decode
@@ -349,6 +367,11 @@ class ModelRunner:
         """Candidates per (row, vocab chunk) on each rank -> (TP: all-gather, 8 B per candidate) -> pick."""
         r = slice(0, B)
         cand = self._cand[B]
+        # penalties first (rows with neutral parameters return at once); the pick appends to the penalised histories.
+        # The pass is launched (and captured: _capture_penalty_graphs) only once a request has asked for penalties
+        if self.hist_used:
+            ops.sample_penalties(self.logits[r], self.active[r], self.pen_meta, self.hist_state, None,
+                                 self.w.vocab_offset, self.cfg.vocab_size)
         ops.sample_candidates(self.logits[r], self.temperature[r], self.top_k[r], self.top_p[r], self.seeds[r],
                               self.positions[r], self.active[r], cand, self.w.vocab_offset)
         if self.comm.size == 1:
@@ -356,8 +379,60 @@ class ModelRunner:
         else:
             cand_all = self._cand_all[B]
             self.comm.all_gather_into(cand_all, cand)
-        ops.sample_pick(cand_all, self.active[r], self.ids[r], self.ring, self.ring_counter, self.positions[r],
-                        vocab=self.cfg.vocab_size)
+        ops.sample_pick_hist(cand_all, self.active[r], self.ids[r], self.ring, self.ring_counter, self.positions[r],
+                             self.pen_meta, self.hist_state, vocab=self.cfg.vocab_size)
+
+    def set_history(self, slot: int, tokens: list, n_prompt: int) -> None:
+        """A penalised sequence takes `slot`: its tokens so far (the submitted prompt, then what it has published)
+        and their count become the slot's history, with one pinned non-blocking copy ordered after every step
+        already enqueued.  The device owns the row afterwards.  (n_prompt itself travels in pen_meta.)"""
+        row = torch.tensor([len(tokens)] + list(tokens), dtype=torch.int32)
+        if row.numel() > self.hist_state.shape[1]:
+            raise ValueError(f"history of {len(tokens)} tokens exceeds max_model_len + 1")
+        if self.device.type == "cuda":
+            row = row.pin_memory()
+        self.hist_state[slot, :row.numel()].copy_(row, non_blocking=True)
+        if not self.hist_used:
+            self.hist_used = True
+            self._capture_penalty_graphs()
+
+    def _capture_penalty_graphs(self) -> None:
+        """The first penalised request: every captured graph gets a twin with the penalty pass in front of the
+        candidates (one more launch per sampled step), replayed from now on; until then the graphs captured at
+        startup run, which hold no such launch (an early-exit launch per step measured +8 us on the 4.23 ms
+        64-stream step: profiles/r7/penalties.md).  Stream capture executes nothing, so no decode state changes;
+        the shapes, buffers and collectives are the ones the startup capture warmed.  Deterministic across a TP
+        group: every rank admits the same request in the same step."""
+        if self._graphs_have_pass or not (self.graphs or self.pf_graphs or self.mx_graphs):
+            return
+        t0 = time.perf_counter()
+        for B in sorted(self.graphs, reverse=True):
+            g = torch.cuda.CUDAGraph()
+            with _capture(g, pool=self.graph_pool):
+                self.decode_forward(B)
+            self.pen_graphs[B] = g
+        for tb in sorted(self.pf_graphs, reverse=True):
+            g = torch.cuda.CUDAGraph()
+            with _capture(g, pool=self.graph_pool):
+                self._prefill_layers(tb, self.pf.views(tb))
+                self._graph_sample()
+            self.pen_pf_graphs[tb] = g
+        for B, C in sorted(((B, C) for B, lst in self.mx_graphs.items() for C, _ in lst), reverse=True):
+            g = torch.cuda.CUDAGraph()
+            with _capture(g, pool=self.graph_pool):
+                self._mixed_layers(B, C)
+                self._graph_sample()
+            self.pen_mx_graphs.setdefault(B, []).insert(0, (C, g))
+        torch.cuda.synchronize(self.device)
+        if self.comm.rank == 0:
+            print(f"[engine] first penalised request: captured the graphs with the penalty pass "
+                  f"({time.perf_counter() - t0:.2f} s)", flush=True)
+
+    def _graph_set(self):
+        """(decode, prefill, mixed) graphs to replay: the twins with the penalty pass once penalties are in use."""
+        if self.hist_used and not self._graphs_have_pass:
+            return self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs
+        return self.graphs, self.pf_graphs, self.mx_graphs
 
     def health_faults(self, words) -> list:
         """Descriptions of the nonzero health words in `words` (a host copy of self.health)."""
@@ -435,6 +510,7 @@ class ModelRunner:
         Neither: eager decode (reason logged)."""
         if not self.use_graphs:
             return
+        self._graphs_have_pass = self.hist_used
         prefill_graphs = True
         if self.comm.size > 1:
             ipc = self.ipc_decode()
@@ -550,10 +626,12 @@ class ModelRunner:
         return next((c for c, _ in self.mx_graphs.get(B, ()) if c >= T), None)
 
     def _snapshot_state(self):
-        return [t.clone() for t in (self.ids, self.positions, self.ring, self.ring_counter)]
+        # hist_len: a warm-up or capture run over a penalised active slot appends to its history (the token written
+        # past the restored length is never read)
+        return [t.clone() for t in (self.ids, self.positions, self.ring, self.ring_counter, self.hist_len)]
 
     def _restore_state(self, saved):
-        for t, s in zip((self.ids, self.positions, self.ring, self.ring_counter), saved):
+        for t, s in zip((self.ids, self.positions, self.ring, self.ring_counter, self.hist_len), saved):
             t.copy_(s)
 
     def move_slots(self, src: list, dst: list) -> None:
@@ -563,11 +641,12 @@ class ModelRunner:
         if self.device.type == "cuda":  # pinned + non_blocking: no host wait for the decode steps already queued
             idx = idx.pin_memory().to(self.device, non_blocking=True)
         si, di = idx[0], idx[1]
-        for t in (self.ids, self.positions):
+        # the token histories (length word + tokens) travel with their slots once any sequence has used penalties
+        for t in (self.ids, self.positions) + ((self.hist_state,) if self.hist_used else ()):
             t.index_copy_(0, di, t.index_select(0, si))
 
     def decode(self, B: int) -> None:
-        g = self.graphs.get(B)
+        g = self._graph_set()[0].get(B)
         if g is not None:
             g.replay()
         else:
@@ -766,6 +845,11 @@ class ModelRunner:
         sd = self.seeds.index_select(0, slot_idx).contiguous()
         nch = SAMPLE_CHUNKS if dev.type == "cuda" else 1
         cand = torch.zeros(nL, nch, 2, **f32)
+        if self.hist_used:  # (an eager pass: nothing is launched until a request has asked for penalties)
+            slot_i32 = slot_idx.to(torch.int32)
+            # after a re-prefill the tokens already published count: the engine uploaded them with the history
+            ops.sample_penalties(logits, None, self.pen_meta, self.hist_state, slot_i32, w.vocab_offset,
+                                 cfg.vocab_size)
         ops.sample_candidates(logits, temp, tk, tp, sd, last_pos, None, cand, w.vocab_offset)
         if comm.size == 1:
             cand_all = cand.unsqueeze(0)
@@ -773,6 +857,8 @@ class ModelRunner:
             cand_all = torch.zeros(comm.size, nL, nch, 2, **f32)
             comm.all_gather_into(cand_all, cand)
         ops.sample_pick(cand_all, None, new_ids, vocab=cfg.vocab_size)
+        if self.hist_used:
+            ops.sample_hist_append(new_ids, slot_i32, None, self.pen_meta, self.hist_state)
         self.ids.index_copy_(0, slot_idx, new_ids)
         self.ring[ring_row].index_copy_(0, slot_idx, new_ids)
         self.positions.index_copy_(0, slot_idx, last_pos + 1)
@@ -787,7 +873,7 @@ class ModelRunner:
         tb = next((t for t in sorted(self.pf_graphs) if t >= T), None) if len(seqs) <= PREFILL_GRAPH_SEQS else None
         if tb is not None:
             self.pf.upload(seqs, tb, ring_row=ring_row)
-            self.pf_graphs[tb].replay()  # first tokens sampled inside the graph (_graph_sample)
+            self._graph_set()[1][tb].replay()  # first tokens sampled inside the graph (_graph_sample)
             return
         w, dev = self.w, self.device
         nh, nkv, F, H = w.nh, w.nkv, w.ffn, self.cfg.hidden_size
@@ -841,6 +927,9 @@ class ModelRunner:
         ops.prefill_sample_gather(pf.x, meta, self.slot_meta, pf.s_xl, sm)
         ops.gemm_out(pf.s_xl, w.lm_head_t, pf.s_logits)
         active = sm[:ns]
+        if self.hist_used:  # gathered row i samples for slot meta[ns + i]: its penalties and history
+            ops.sample_penalties(pf.s_logits, active, self.pen_meta, self.hist_state, meta[ns:2 * ns],
+                                 w.vocab_offset, cfg.vocab_size)
         ops.sample_candidates(pf.s_logits, sm[ns:2 * ns].view(torch.float32), sm[2 * ns:3 * ns],
                               sm[3 * ns:4 * ns].view(torch.float32), sm[4 * ns:6 * ns].view(ns, 2), sm[6 * ns:7 * ns],
                               active, pf.s_cand, w.vocab_offset)
@@ -850,7 +939,8 @@ class ModelRunner:
             cand_all = pf.s_cand_all
             comm.all_gather_into(cand_all, pf.s_cand)
         ops.sample_pick(cand_all, active, pf.s_new, vocab=cfg.vocab_size)
-        ops.prefill_sample_commit(meta, pf.s_new, self.ids, self.ring, self.positions)
+        ops.prefill_sample_commit_hist(meta, pf.s_new, self.ids, self.ring, self.positions, self.pen_meta,
+                                       self.hist_state)
 
     def mixed(self, B: int, seqs: list, ring_row: int) -> None:
         """ONE forward over the decode slots [0, B) and the prefill chunks `seqs` (rows B .. B+T-1): every weight
@@ -864,7 +954,7 @@ class ModelRunner:
         prompt sample their first token as prefill() does.  Same tokens as prefill() + decode() (greedy:
         tests/test_mixed_step.py)."""
         T = sum(len(s.tokens) for s in seqs)
-        entry = next(((c, g) for c, g in self.mx_graphs.get(B, ()) if c >= T), None)
+        entry = next(((c, g) for c, g in self._graph_set()[2].get(B, ()) if c >= T), None)
         if entry is not None and len(seqs) <= PREFILL_GRAPH_SEQS:
             t0 = time.perf_counter()
             self.pf.upload(seqs, entry[0], row0=B, ring_row=ring_row)

@@ -247,6 +247,43 @@ def prefill_sample_commit(meta, new_ids, ids, ring, positions):
         ref.prefill_sample_commit(meta, new_ids, ids, ring, positions)
 
 
+def sample_penalties(logits, active, pen_meta, hist, row_slot=None, vocab_offset=0, vocab: int = 2**31 - 1):
+    """Presence / frequency / repetition penalties, in place on logits [B, V] (row stride >= V) before
+    sample_candidates.  pen_meta int32 [4 Bm] = [presence | frequency | repetition (float32 bits) | n_prompt] per
+    slot; hist int32 [Bm, capacity + 1] = [tokens held | prompt then generated tokens]; row b is slot row_slot[b]
+    (else b).  Inactive rows and rows with neutral parameters keep their logits bit for bit."""
+    if _hip(logits):
+        torch.ops.dsse.sample_penalties(logits, active, pen_meta, hist, row_slot, vocab_offset, vocab)
+    else:
+        ref.sample_penalties(logits, active, pen_meta, hist, row_slot, vocab_offset, vocab)
+
+
+def sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,
+                     vocab: int = 2**31 - 1):
+    """sample_pick whose picked token also joins hist[b] (device-side, stream-ordered) where slot b has penalties."""
+    if _hip(cand_all):
+        torch.ops.dsse.sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,
+                                        vocab)
+    else:
+        ref.sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist, vocab)
+
+
+def prefill_sample_commit_hist(meta, new_ids, ids, ring, positions, pen_meta, hist):
+    """prefill_sample_commit whose first tokens also join the history of the slots that have penalties."""
+    if _hip(new_ids):
+        torch.ops.dsse.prefill_sample_commit_hist(meta, new_ids, ids, ring, positions, pen_meta, hist)
+    else:
+        ref.prefill_sample_commit_hist(meta, new_ids, ids, ring, positions, pen_meta, hist)
+
+
+def sample_hist_append(new_ids, row_slot, active, pen_meta, hist):
+    """hist[slot] += new_ids[i] (slot = row_slot[i], else i) for active rows whose slot has penalties."""
+    if _hip(new_ids):
+        torch.ops.dsse.sample_hist_append(new_ids, row_slot, active, pen_meta, hist)
+    else:
+        ref.sample_hist_append(new_ids, row_slot, active, pen_meta, hist)
+
+
 def sample(logits, temperature, top_k, top_p, seeds, positions, active, next_ids, ring=None, ring_counter=None,
            positions_inc=None, nchunks: int = 16):
     """Single-rank convenience: candidates + pick."""

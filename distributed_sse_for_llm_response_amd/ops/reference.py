@@ -337,3 +337,84 @@ def prefill_sample_commit(meta, new_ids, ids, ring, positions):
         ids[slot] = new_ids[i]
         ring[row, slot] = new_ids[i]
         positions[slot] = int(meta[2 * NS + i]) + 1
+
+
+# ---- presence / frequency / repetition penalties (sampler.hip sample_penalty_kernel and the history append) ----
+# Per-slot state: pen_meta int32 [4 Bm] = [presence | frequency | repetition (float32 bits) | n_prompt] and
+# hist int32 [Bm, capacity + 1]: word 0 = tokens held, then the prompt followed by the generated tokens.
+def _pen_params(pen_meta, slot: int):
+    Bm = pen_meta.numel() // 4
+    f = pen_meta.view(torch.float32)
+    return float(f[slot]), float(f[Bm + slot]), float(f[2 * Bm + slot]), int(pen_meta[3 * Bm + slot])
+
+
+def penalties_on(pen_meta, slot: int) -> bool:
+    p, f, r, _ = _pen_params(pen_meta, slot)
+    return p != 0.0 or f != 0.0 or r != 1.0
+
+
+def sample_penalties(logits, active, pen_meta, hist, row_slot=None, vocab_offset=0, vocab: int = 2**31 - 1):
+    """In place on logits [B, V] (row b = slot row_slot[b], else b), in the logits' own dtype; with c[v] = the
+    occurrences of v among the generated tokens: every v in the prompt or generated gets x = x / r if x > 0 else
+    x * r; then x -= f c[v]; then x -= p where c[v] > 0.  Inactive rows and rows whose parameters are neutral
+    (p = f = 0, r = 1) are not touched; history tokens outside [vocab_offset, vocab_offset + V) are skipped."""
+    B, V = logits.shape
+    for b in range(B):
+        if active is not None and not int(active[b]):
+            continue
+        slot = int(row_slot[b]) if row_slot is not None else b
+        if not penalties_on(pen_meta, slot):
+            continue
+        p, f, r, n_prompt = _pen_params(pen_meta, slot)
+        n = min(max(int(hist[slot, 0]), 0), hist.shape[1] - 1)
+        toks = hist[slot, 1:1 + n].tolist()
+        seen, cnt = set(), {}
+        for j, t in enumerate(toks):
+            v = t - vocab_offset
+            if not 0 <= v < V:
+                continue
+            seen.add(v)
+            if j >= n_prompt:
+                cnt[v] = cnt.get(v, 0) + 1
+        for v in seen:
+            x = logits[b, v]
+            if r != 1.0:
+                x = x / r if x > 0 else x * r
+            c = cnt.get(v, 0)
+            x = x - f * c
+            if c > 0:
+                x = x - p
+            logits[b, v] = x
+
+
+def _hist_append(pen_meta, hist, slot: int, tok: int) -> None:
+    if not penalties_on(pen_meta, slot):
+        return
+    n = int(hist[slot, 0])
+    if 0 <= n < hist.shape[1] - 1:
+        hist[slot, 1 + n] = tok
+        hist[slot, 0] = n + 1
+
+
+def sample_hist_append(new_ids, row_slot, active, pen_meta, hist):
+    """hist[slot] += new_ids[i] for the active rows whose slot (row_slot[i], else i) has penalties on."""
+    for i in range(new_ids.numel()):
+        if active is not None and not int(active[i]):
+            continue
+        _hist_append(pen_meta, hist, int(row_slot[i]) if row_slot is not None else i, int(new_ids[i]))
+
+
+def sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,
+                     vocab: int = 2**31 - 1):
+    """sample_pick, then the picked token of every active penalised row (row b = slot b) joins its history."""
+    sample_pick(cand_all, active, next_ids, ring, ring_counter, positions_inc, vocab)
+    sample_hist_append(next_ids[:cand_all.shape[1]], None, active, pen_meta, hist)
+
+
+def prefill_sample_commit_hist(meta, new_ids, ids, ring, positions, pen_meta, hist):
+    """prefill_sample_commit, then the first token of every finishing prompt whose slot has penalties on joins its
+    history."""
+    prefill_sample_commit(meta, new_ids, ids, ring, positions)
+    NS = new_ids.numel()
+    for i in range(min(int(meta[3 * NS]), NS)):
+        _hist_append(pen_meta, hist, int(meta[NS + i]), int(new_ids[i]))

@@ -110,7 +110,11 @@ class EngineLoop(threading.Thread):
             top_p=req["top_p"] if 0 < req["top_p"] <= 1 else d.top_p,
             top_k=req["top_k"] if req["top_k"] > 0 else d.top_k,
             max_tokens=req["max_tokens"] if req["max_tokens"] > 0 else d.max_tokens,
-            seed=req["seed"] if req["seed"] >= 0 else None, ignore_eos=bool(req.get("ignore_eos", False)))
+            seed=req["seed"] if req["seed"] >= 0 else None, ignore_eos=bool(req.get("ignore_eos", False)),
+            # (range-checked by the HTTP server; a request without them carries the neutral values)
+            presence_penalty=float(req.get("presence_penalty", d.presence_penalty)),
+            frequency_penalty=float(req.get("frequency_penalty", d.frequency_penalty)),
+            repetition_penalty=float(req.get("repetition_penalty", d.repetition_penalty)))
 
     def flow_events(self) -> list:
         """Flow-control transitions from the runtime plus pauses that outlived ``max_pause_s``."""
