@@ -112,6 +112,30 @@ struct SampleParams {
   const int* row_slot;       // [B] slot of logits row b, or null (row b = slot b)
 };
 
+// Log-probabilities of the sampled token and the top-N (sampler.hip logprob_*_kernel): raw logprobs, x - logsumexp(x)
+// over the full vocabulary of the fp32 logits as the LM head wrote them (before penalties / temperature / filters).
+constexpr int kLpTop = 20;               // top_logprobs at most
+constexpr int kLpRec = 2 + 2 * kLpTop;   // per-(rank, row) record: [max | sum exp(x - max) | kLpTop x (logit, id bits)]
+constexpr int kLpOut = 1 + 2 * kLpTop;   // per-token result: [logprob of the sampled token | kLpTop ids | kLpTop logprobs]
+struct LogprobParams {
+  const float* logits;    // [B, ld] this rank's shard (stats / chosen passes)
+  int ld, V, vocab_offset, v_global;
+  const int* active;      // [B] or null
+  const int* lp_meta;     // [slots]: -1 = off, 0..kLpTop = N
+  int slots;
+  const int* row_slot;    // [B] slot of row b, or null (row b = slot b)
+  float* rec;             // stats: [B, kLpRec] out;  finish: [world, B, kLpRec] in
+  float* raw;             // stats: [B, V] copy of the rows with logprobs on (the penalty pass rewrites logits), or null
+  const int* next_ids;    // chosen: [B] sampled (global) ids
+  float* chosen;          // chosen: [B] out;  finish: [world, B] in
+  int world;
+  float* lp_ring;         // finish: [ring_size, slots, kLpOut]
+  int ring_size;
+  const int* ring_counter;  // ring row = ring_counter[0] % ring_size, else ring_row_dev[0], else ring_row
+  const int* ring_row_dev;
+  int ring_row;
+};
+
 }  // namespace dsse
 
 extern "C" {
@@ -140,6 +164,9 @@ hipError_t dsse_prefill_sample_commit(const int* meta, int NS, const int* new_id
                                       int* positions, const int* pen_meta, int* hist, int hist_ld, hipStream_t st);
 hipError_t dsse_sample_penalties(int B, float* logits, const dsse::SampleParams* p, hipStream_t st);
 hipError_t dsse_sample_hist_append(int n, const int* new_ids, const dsse::SampleParams* p, hipStream_t st);
+hipError_t dsse_logprob_stats(int B, const dsse::LogprobParams* p, hipStream_t st);
+hipError_t dsse_logprob_chosen(int B, const dsse::LogprobParams* p, hipStream_t st);
+hipError_t dsse_logprob_finish(int B, const dsse::LogprobParams* p, hipStream_t st);
 hipError_t dsse_rmsnorm(int mode, int M, float* resid, int H, const void* delta, const void* embed,
                         const int* ids, const void* w, void* y, float eps, const float* part, int nsplit,
                         int vocab, hipStream_t st);

@@ -1196,6 +1196,135 @@ void prefill_sample_commit_hist(const Tensor& meta, const Tensor& new_ids, Tenso
   prefill_sample_commit_impl(meta, new_ids, ids, ring, positions, &pen_meta, &hist);
 }
 
+// ---- logprobs / top_logprobs (sampler.hip logprob_*_kernel) ---------------------------------------------------
+// lp_meta: int32 [slots], -1 = off, 0..20 = N; row b is slot row_slot[b] (else b).
+void logprob_rows(dsse::LogprobParams& p, const c10::optional<Tensor>& active, const Tensor& lp_meta,
+                  const c10::optional<Tensor>& row_slot, int B) {
+  check_gpu(lp_meta, "lp_meta");
+  check_dtype(lp_meta, at::kInt, "lp_meta");
+  TORCH_CHECK(lp_meta.is_contiguous() && lp_meta.numel() >= 1, "lp_meta must be a contiguous [slots]");
+  p.lp_meta = lp_meta.data_ptr<int>();
+  p.slots = (int)lp_meta.numel();
+  if (active.has_value()) {
+    check_gpu(*active, "active");
+    check_dtype(*active, at::kInt, "active");
+    TORCH_CHECK(active->is_contiguous() && active->numel() >= B, "active too short");
+    p.active = active->data_ptr<int>();
+  }
+  if (row_slot.has_value()) {
+    check_gpu(*row_slot, "row_slot");
+    check_dtype(*row_slot, at::kInt, "row_slot");
+    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
+    p.row_slot = row_slot->data_ptr<int>();
+  } else {
+    TORCH_CHECK(B <= p.slots, "more rows than slots (no row_slot map)");
+  }
+}
+
+void logprob_logits(dsse::LogprobParams& p, const Tensor& logits, int64_t vocab_offset, int64_t vocab) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");  // (rows may be strided: a column slice of a shard)
+  check_dtype(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
+                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= 32768, "sampler supports V <= 32768 per rank");
+  TORCH_CHECK(vocab_offset >= 0 && vocab_offset <= INT32_MAX - 32768, "vocab_offset out of range");
+  p.logits = logits.data_ptr<float>();
+  p.ld = (int)logits.stride(0);
+  p.V = (int)logits.size(1);
+  p.vocab_offset = (int)vocab_offset;
+  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
+}
+
+// Per-rank pass over logits [B, V] BEFORE the penalty pass: rec [B, 42] = [max | sum exp(x - max) | 20 x (logit, id
+// bits)] of the rows whose slot has logprobs on (other rows untouched); raw [>= B, V] (optional) receives a copy of
+// those rows for logprob_chosen.
+void logprob_stats(const Tensor& logits, const c10::optional<Tensor>& active, const Tensor& lp_meta,
+                   const c10::optional<Tensor>& row_slot, Tensor& rec, const c10::optional<Tensor>& raw,
+                   int64_t vocab_offset) {
+  dsse::LogprobParams p{};
+  logprob_logits(p, logits, vocab_offset, INT32_MAX);
+  const int B = (int)logits.size(0);
+  logprob_rows(p, active, lp_meta, row_slot, B);
+  check_gpu(rec, "rec");
+  check_dtype(rec, at::kFloat, "rec");
+  TORCH_CHECK(rec.is_contiguous() && rec.dim() == 2 && rec.size(0) >= B && rec.size(1) == dsse::kLpRec,
+              "rec must be a contiguous [>= B, 42]");
+  p.rec = rec.data_ptr<float>();
+  if (raw.has_value()) {
+    check_gpu(*raw, "raw");
+    check_dtype(*raw, at::kFloat, "raw");
+    TORCH_CHECK(raw->is_contiguous() && raw->dim() == 2 && raw->size(0) >= B && raw->size(1) == p.V,
+                "raw must be a contiguous [>= B, V]");
+    p.raw = raw->data_ptr<float>();
+  }
+  DSSE_CHECK_HIP(dsse_logprob_stats(B, &p, cur_stream()));
+}
+
+// chosen[b] = logits[b, next_ids[b] - vocab_offset] where this shard owns the id, else -inf (rows with logprobs on).
+void logprob_chosen(const Tensor& logits, const Tensor& next_ids, const c10::optional<Tensor>& active,
+                    const Tensor& lp_meta, const c10::optional<Tensor>& row_slot, Tensor& chosen,
+                    int64_t vocab_offset, int64_t vocab) {
+  dsse::LogprobParams p{};
+  logprob_logits(p, logits, vocab_offset, vocab);
+  const int B = (int)logits.size(0);
+  logprob_rows(p, active, lp_meta, row_slot, B);
+  check_gpu(next_ids, "next_ids");
+  check_dtype(next_ids, at::kInt, "next_ids");
+  check_gpu(chosen, "chosen");
+  check_dtype(chosen, at::kFloat, "chosen");
+  TORCH_CHECK(next_ids.is_contiguous() && next_ids.numel() >= B && chosen.is_contiguous() && chosen.numel() >= B,
+              "next_ids / chosen too short");
+  p.next_ids = next_ids.data_ptr<int>();
+  p.chosen = chosen.data_ptr<float>();
+  DSSE_CHECK_HIP(dsse_logprob_chosen(B, &p, cur_stream()));
+}
+
+// Merge rec_all [world, B, 42] and chosen_all [world, B] and write [logprob of the sampled token | 20 ids | 20
+// logprobs] to lp_ring[row, slot]; row = ring_counter[0] % R, else ring_row_dev[0], else ring_row.
+void logprob_finish(const Tensor& rec_all, const Tensor& chosen_all, const c10::optional<Tensor>& active,
+                    const Tensor& lp_meta, const c10::optional<Tensor>& row_slot, Tensor& lp_ring,
+                    const c10::optional<Tensor>& ring_counter, const c10::optional<Tensor>& ring_row_dev,
+                    int64_t ring_row, int64_t vocab) {
+  check_gpu(rec_all, "rec_all");
+  check_dtype(rec_all, at::kFloat, "rec_all");
+  check_gpu(chosen_all, "chosen_all");
+  check_dtype(chosen_all, at::kFloat, "chosen_all");
+  check_gpu(lp_ring, "lp_ring");
+  check_dtype(lp_ring, at::kFloat, "lp_ring");
+  TORCH_CHECK(rec_all.is_contiguous() && rec_all.dim() == 3 && rec_all.size(2) == dsse::kLpRec &&
+                  rec_all.size(0) >= 1 && rec_all.size(0) <= 8, "rec_all must be a contiguous [world <= 8, B, 42]");
+  const int world = (int)rec_all.size(0), B = (int)rec_all.size(1);
+  TORCH_CHECK(chosen_all.is_contiguous() && chosen_all.dim() == 2 && chosen_all.size(0) == world &&
+                  chosen_all.size(1) == B, "chosen_all must be a contiguous [world, B]");
+  dsse::LogprobParams p{};
+  logprob_rows(p, active, lp_meta, row_slot, B);
+  TORCH_CHECK(lp_ring.is_contiguous() && lp_ring.dim() == 3 && lp_ring.size(1) == p.slots &&
+                  lp_ring.size(2) == dsse::kLpOut && lp_ring.size(0) >= 1 && lp_ring.size(0) <= INT32_MAX,
+              "lp_ring must be a contiguous [R, slots, 41]");
+  p.rec = rec_all.data_ptr<float>();
+  p.chosen = chosen_all.data_ptr<float>();
+  p.world = world;
+  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
+  p.lp_ring = lp_ring.data_ptr<float>();
+  p.ring_size = (int)lp_ring.size(0);
+  p.ring_row = -1;
+  if (ring_counter.has_value()) {
+    check_gpu(*ring_counter, "ring_counter");
+    check_dtype(*ring_counter, at::kInt, "ring_counter");
+    TORCH_CHECK(ring_counter->numel() >= 1, "ring_counter is empty");
+    p.ring_counter = ring_counter->data_ptr<int>();
+  } else if (ring_row_dev.has_value()) {
+    check_gpu(*ring_row_dev, "ring_row_dev");
+    check_dtype(*ring_row_dev, at::kInt, "ring_row_dev");
+    TORCH_CHECK(ring_row_dev->numel() >= 1, "ring_row_dev is empty");
+    p.ring_row_dev = ring_row_dev->data_ptr<int>();
+  } else {
+    TORCH_CHECK(ring_row >= 0 && ring_row < lp_ring.size(0), "ring_row outside the ring");
+    p.ring_row = (int)ring_row;
+  }
+  DSSE_CHECK_HIP(dsse_logprob_finish(B, &p, cur_stream()));
+}
+
 // ---- TP all-reduce over IPC peer buffers (allreduce.hip) ------------------------------------------------------
 // ar_alloc: this rank's zeroed buffer for `rows` decode rows of width H -> (64-byte IPC handle as uint8 [64],
 // device pointer, uncached flag).  ar_open: a peer's handle -> its pointer in this process.  The buffers live
@@ -1411,6 +1540,13 @@ TORCH_LIBRARY(dsse, m) {
   m.def("prefill_sample_commit_hist(Tensor meta, Tensor new_ids, Tensor(a!) ids, Tensor(b!) ring, "
         "Tensor(c!) positions, Tensor pen_meta, Tensor(d!) hist) -> ()");
   m.def("sample_hist_append(Tensor new_ids, Tensor? row_slot, Tensor? active, Tensor pen_meta, Tensor(a!) hist) -> ()");
+  m.def("logprob_stats(Tensor logits, Tensor? active, Tensor lp_meta, Tensor? row_slot, Tensor(a!) rec, "
+        "Tensor(b!)? raw=None, int vocab_offset=0) -> ()");
+  m.def("logprob_chosen(Tensor logits, Tensor next_ids, Tensor? active, Tensor lp_meta, Tensor? row_slot, "
+        "Tensor(a!) chosen, int vocab_offset=0, int vocab=2147483647) -> ()");
+  m.def("logprob_finish(Tensor rec_all, Tensor chosen_all, Tensor? active, Tensor lp_meta, Tensor? row_slot, "
+        "Tensor(a!) lp_ring, Tensor? ring_counter=None, Tensor? ring_row_dev=None, int ring_row=-1, "
+        "int vocab=2147483647) -> ()");
   m.def("ar_alloc(int rows, int H) -> (Tensor, int, int)", &ar_alloc);
   m.def("ar_open(Tensor handle) -> int", &ar_open);
   m.def("ar_close(int ptr, bool opened) -> ()", &ar_close);
@@ -1452,6 +1588,9 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("sample_pick_hist", &sample_pick_hist);
   m.impl("prefill_sample_commit_hist", &prefill_sample_commit_hist);
   m.impl("sample_hist_append", &sample_hist_append);
+  m.impl("logprob_stats", &logprob_stats);
+  m.impl("logprob_chosen", &logprob_chosen);
+  m.impl("logprob_finish", &logprob_finish);
   m.impl("ar_rmsnorm", &ar_rmsnorm);
   m.impl("ar_gather", &ar_gather);
 }

@@ -307,7 +307,193 @@ __global__ void prefill_sample_commit_kernel(const int* __restrict__ meta, int N
   if (hist) hist_append(pen_meta, Bm, hist, hist_ld, slot, new_ids[i]);
 }
 
+// ---- logprobs / top_logprobs ---------------------------------------------------------------------------------
+// Raw logprobs (vLLM's default): lp[v] = x[v] - logsumexp(x) over the full vocabulary of the fp32 logits as the LM
+// head wrote them.  Per-slot state lp_meta[slot] (host-owned, uploaded with the slot metadata): -1 = off, 0..kLpTop
+// = N.  top-N order: logit descending, equal logits by ascending global id -- `better` on the stored fp32 values,
+// so the ids are the same under every vocab sharding.
+DEV int lp_rows_n(const LogprobParams& p, int b, int* slot_out) {
+  if (p.active && !p.active[b]) return -1;
+  const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, p.slots, -1);
+  if (slot < 0) return -1;
+  *slot_out = slot;
+  return min(p.lp_meta[slot], kLpTop);
+}
+
+DEV int block_min_int(int v, int* sh) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int tot = 0x7fffffff;
+  for (int i = 0; i < kSThreads / 64; ++i) tot = min(tot, sh[i]);
+  __syncthreads();
+  return tot;
+}
+
+// One workgroup per logits row of this rank's shard; a row that is inactive or off returns at once.  The row is
+// staged once in LDS (and copied to p.raw when given: the penalty pass that follows rewrites logits in place), then:
+// m = max, s = sum exp(x - m), and the shard's top-N: the radix select gives the N-th key, everything above it is
+// taken, and the entries equal to it are admitted lowest id first (a tie across the N boundary resolves the same
+// way on every rank layout); the <= kLpTop survivors are ordered by counting.  Record: [m | s | kLpTop x (logit,
+// global id bits)], unused entries (-inf, 0x7fffffff).
+__global__ void __launch_bounds__(kSThreads) logprob_stats_kernel(LogprobParams p) {
+  const int b = blockIdx.x;
+  int slot = 0;
+  const int N = lp_rows_n(p, b, &slot);
+  if (N < 0) return;
+  __shared__ float xs[kSMaxV];
+  __shared__ float hist[256];
+  __shared__ float sh[kSThreads / 64];
+  __shared__ int shi[kSThreads / 64];
+  __shared__ float tl[kLpTop];
+  __shared__ int ti[kLpTop];
+  __shared__ int s_n;
+  const float* row = p.logits + (size_t)b * p.ld;
+  float* raw = p.raw ? p.raw + (size_t)b * p.V : nullptr;
+  float lmax = -INFINITY;
+  for (int i = threadIdx.x; i < p.V; i += kSThreads) {
+    const float x = row[i];
+    if (raw) raw[i] = x;
+    xs[i] = x + 0.f;  // -0 -> +0: the radix keys then order exactly as the float compare of the merge does
+    lmax = fmaxf(lmax, x);
+  }
+  if (threadIdx.x == 0) s_n = 0;
+  const float m = block_max(lmax, sh);  // (barriers: xs and s_n are visible)
+  float z = 0.f;
+  if (m > -INFINITY)
+    for (int i = threadIdx.x; i < p.V; i += kSThreads) z += expf(xs[i] - m);
+  z = block_sum(z, sh);
+  float* rec = p.rec + (size_t)b * kLpRec;
+  const int n_take = min(N, p.V);
+  int cnt = 0;
+  if (n_take > 0) {
+    const uint32_t thr = radix_select<false>(xs, p.V, m, 0u, (float)n_take, hist);
+    for (int i = threadIdx.x; i < p.V; i += kSThreads)
+      if (fkey(xs[i]) > thr) {
+        const int j = atomicAdd(&s_n, 1);  // fewer than n_take by the select's definition
+        if (j < kLpTop) { tl[j] = xs[i]; ti[j] = i + p.vocab_offset; }
+      }
+    __syncthreads();
+    cnt = min(s_n, n_take);
+    int last = -1;
+    while (cnt < n_take) {  // the ties at the threshold, lowest id first (usually one entry, one round)
+      int mn = 0x7fffffff;
+      for (int i = threadIdx.x; i < p.V; i += kSThreads)
+        if (i > last && fkey(xs[i]) == thr) { mn = i; break; }
+      mn = block_min_int(mn, shi);
+      if (mn == 0x7fffffff) break;
+      if (threadIdx.x == 0) { tl[cnt] = xs[mn]; ti[cnt] = mn + p.vocab_offset; }
+      last = mn;
+      ++cnt;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { rec[0] = m; rec[1] = z; }
+  if (threadIdx.x < kLpTop) {
+    const int t = threadIdx.x;
+    if (t < cnt) {
+      const float l = tl[t];
+      const int id = ti[t];
+      int rank = 0;
+      for (int j = 0; j < cnt; ++j) rank += (tl[j] > l || (tl[j] == l && ti[j] < id)) ? 1 : 0;
+      rec[2 + 2 * rank] = l;
+      rec[3 + 2 * rank] = __int_as_float(id);
+    } else {
+      rec[2 + 2 * t] = -INFINITY;
+      rec[3 + 2 * t] = __int_as_float(0x7fffffff);
+    }
+  }
+}
+
+// chosen[b] = this shard's raw logit of the sampled token next_ids[b], -inf when another shard owns it (TP: one 4 B
+// all-gather per row, then the finish pass takes the max).  `logits` is p.raw's copy where the penalty pass ran.
+__global__ void logprob_chosen_kernel(int B, LogprobParams p) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int slot = 0;
+  if (lp_rows_n(p, b, &slot) < 0) return;
+  const int v = DSSE_IDX(p.next_ids[b], p.v_global, -1) - p.vocab_offset;
+  p.chosen[b] = (unsigned)v < (unsigned)p.V ? p.logits[(size_t)b * p.ld + v] : -INFINITY;
+}
+
+// One 64-thread workgroup per row: merge the `world` records -- M = max m_w, lse = M + log sum s_w exp(m_w - M)
+// (an empty or all -inf shard has s_w = 0 and m_w = -inf: it adds nothing and is skipped, so no inf - inf), the
+// world x kLpTop candidates ranked by counting in the same order -- subtract lse and write [logprob of the sampled
+// token | kLpTop ids | kLpTop logprobs] to lp_ring[ring row][slot], where the token itself went; entries past
+// min(N, vocab) are (-1, -inf).
+__global__ void __launch_bounds__(64) logprob_finish_kernel(int B, LogprobParams p) {
+  const int b = blockIdx.x;
+  int slot = 0;
+  const int N = lp_rows_n(p, b, &slot);
+  if (N < 0) return;
+  constexpr int kMaxWorld = 8;
+  __shared__ float cl[kMaxWorld * kLpTop];
+  __shared__ int ci[kMaxWorld * kLpTop];
+  const int nc = p.world * kLpTop;
+  float M = -INFINITY, chosen = -INFINITY;
+  for (int w = 0; w < p.world; ++w) {
+    M = fmaxf(M, p.rec[((size_t)w * B + b) * kLpRec]);
+    chosen = fmaxf(chosen, p.chosen[(size_t)w * B + b]);
+  }
+  float s = 0.f;
+  for (int w = 0; w < p.world; ++w) {
+    const float* r = p.rec + ((size_t)w * B + b) * kLpRec;
+    if (r[0] > -INFINITY && r[1] > 0.f) s += r[1] * expf(r[0] - M);
+  }
+  const float lse = s > 0.f ? M + logf(s) : -INFINITY;
+  for (int c = threadIdx.x; c < nc; c += 64) {
+    const float* r = p.rec + ((size_t)(c / kLpTop) * B + b) * kLpRec + 2 + 2 * (c % kLpTop);
+    cl[c] = r[0];
+    ci[c] = __float_as_int(r[1]);
+  }
+  __syncthreads();
+  int row = p.ring_counter ? p.ring_counter[0] % p.ring_size : (p.ring_row_dev ? p.ring_row_dev[0] : p.ring_row);
+  row = DSSE_IDX(row, p.ring_size, 0);
+  float* out = p.lp_ring + ((size_t)row * p.slots + slot) * kLpOut;
+  if (threadIdx.x == 0) out[0] = chosen > -INFINITY ? chosen - lse : -INFINITY;
+  for (int c = threadIdx.x; c < nc; c += 64) {
+    const float l = cl[c];
+    const int id = ci[c];
+    int rank = 0;
+    for (int j = 0; j < nc; ++j)
+      rank += (cl[j] > l || (cl[j] == l && (ci[j] < id || (ci[j] == id && j < c)))) ? 1 : 0;
+    if (rank >= kLpTop) continue;
+    const bool used = rank < N && id != 0x7fffffff;
+    out[1 + rank] = __int_as_float(used ? DSSE_IDX(id, p.v_global, 0) : -1);
+    out[1 + kLpTop + rank] = used && l > -INFINITY ? l - lse : -INFINITY;
+  }
+}
+
 }  // namespace dsse
+
+extern "C" hipError_t dsse_logprob_stats(int B, const dsse::LogprobParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (p->V > dsse::kSMaxV || p->V < 1 || p->ld < p->V || !p->logits || !p->lp_meta || !p->rec || p->slots < 1 ||
+      (!p->row_slot && B > p->slots))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::logprob_stats_kernel, dim3(B), dim3(dsse::kSThreads), 0, st, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t dsse_logprob_chosen(int B, const dsse::LogprobParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (p->V < 1 || p->ld < p->V || !p->logits || !p->lp_meta || !p->next_ids || !p->chosen || p->slots < 1 ||
+      (!p->row_slot && B > p->slots))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::logprob_chosen_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t dsse_logprob_finish(int B, const dsse::LogprobParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (p->world < 1 || p->world > 8 || !p->lp_meta || !p->rec || !p->chosen || !p->lp_ring || p->slots < 1 ||
+      p->ring_size < 1 || (!p->row_slot && B > p->slots) ||
+      (!p->ring_counter && !p->ring_row_dev && (p->ring_row < 0 || p->ring_row >= p->ring_size)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::logprob_finish_kernel, dim3(B), dim3(64), 0, st, B, *p);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t dsse_prefill_sample_gather(const void* x, int T, int H, const int* meta, int NS,
                                                  const int* slot_meta, int Bm, void* xl, int* smeta, hipStream_t st) {

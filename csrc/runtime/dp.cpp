@@ -34,6 +34,7 @@ std::string encode_request(const ChatRequest& r) {
   w.f64(r.presence_penalty);
   w.f64(r.frequency_penalty);
   w.f64(r.repetition_penalty);
+  w.i32(r.logprobs);
   return w.data();
 }
 
@@ -53,6 +54,7 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   r->presence_penalty = rd.f64();
   r->frequency_penalty = rd.f64();
   r->repetition_penalty = rd.f64();
+  r->logprobs = rd.i32();
   return rd.good();
 }
 }  // namespace dpwire
@@ -263,6 +265,7 @@ void DpRouter::handle_tokens(int w, dpwire::Reader& rd) {
     std::string text = rd.str();
     m.finish = rd.u8();
     m.prompt_tokens = rd.i32();
+    m.logprobs = rd.str();
     if (!text.empty()) m.token = std::move(text);
     else if (tok >= 0 && (size_t)tok < vocab->size()) m.token = (*vocab)[(size_t)tok];
     else m.token = "<" + std::to_string(tok) + ">";
@@ -378,7 +381,7 @@ std::vector<ChatRequest> DpWorker::poll(size_t max, int timeout_ms, std::vector<
 bool DpWorker::publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                               const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                               const std::vector<std::string>& texts, const std::vector<int>& finish,
-                              const std::vector<int>& prompt_tokens) {
+                              const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs) {
   const size_t n = conv_ids.size();
   dpwire::Writer m;
   m.u8(dpwire::kTokens);
@@ -393,6 +396,7 @@ bool DpWorker::publish_tokens(const std::vector<std::string>& conv_ids, const st
     m.str(i < texts.size() ? texts[i] : empty);
     m.u8(i < finish.size() ? (uint8_t)finish[i] : 0);
     m.i32(i < prompt_tokens.size() ? prompt_tokens[i] : -1);
+    m.str(i < logprobs.size() ? logprobs[i] : empty);
   }
   return send(m.data());
 }

@@ -149,7 +149,8 @@ class DpWorker {
   bool publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                       const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                       const std::vector<std::string>& texts, const std::vector<int>& finish = {},
-                      const std::vector<int>& prompt_tokens = {});
+                      const std::vector<int>& prompt_tokens = {},
+                      const std::vector<std::string>& logprobs = {});
   void hello();
   void bye();
   void stats(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,

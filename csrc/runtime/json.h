@@ -27,6 +27,9 @@ struct TokenMessage {
   int64_t timestamp = 0;
   uint8_t finish = kFinishNone;  // terminal messages from the engine
   int32_t prompt_tokens = -1;    // terminal messages from the engine: prompt length (-1 = unknown)
+  // OpenAI logprobs entry of this token, ready-made JSON ({"token":..,"logprob":..,"bytes":[..],"top_logprobs":[..]});
+  // empty = none.  Like finish / prompt_tokens it rides along in the Frame, outside the wire JSON.
+  std::string logprobs;
 };
 
 // Append a JSON string literal (with quotes) using Go json.Marshal escaping rules.

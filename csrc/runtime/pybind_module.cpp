@@ -40,6 +40,7 @@ py::dict request_dict(const ChatRequest& r) {
   d["presence_penalty"] = r.presence_penalty;
   d["frequency_penalty"] = r.frequency_penalty;
   d["repetition_penalty"] = r.repetition_penalty;
+  d["logprobs"] = r.logprobs;
   d["from_edge"] = r.from_edge;
   d["messages"] = r.messages_json;
   return d;
@@ -157,7 +158,7 @@ class Runtime {
   int publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                      const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                      const std::vector<std::string>& texts, const std::vector<int>& finish,
-                     const std::vector<int>& prompt_tokens) {
+                     const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs) {
     const size_t n = conv_ids.size();
     if (token_ids.size() != n || seqs.size() != n || dones.size() != n)
       throw std::invalid_argument("publish_tokens: length mismatch");
@@ -177,6 +178,8 @@ class Runtime {
         m.timestamp = t;
         m.finish = i < finish.size() ? (uint8_t)finish[i] : kFinishNone;
         m.prompt_tokens = i < prompt_tokens.size() ? prompt_tokens[i] : -1;
+        if (i < logprobs.size()) m.logprobs = logprobs[i];
+        else m.logprobs.clear();
         frames.push_back(Bus::make_frame(m));
       }
       bus_->publish_batch(frames);
@@ -249,12 +252,12 @@ class DpWorkerPy {
   int publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                      const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                      const std::vector<std::string>& texts, const std::vector<int>& finish,
-                     const std::vector<int>& prompt_tokens) {
+                     const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs) {
     const size_t n = conv_ids.size();
     if (token_ids.size() != n || seqs.size() != n || dones.size() != n)
       throw std::invalid_argument("publish_tokens: length mismatch");
     py::gil_scoped_release nogil;
-    if (!w_->publish_tokens(conv_ids, token_ids, seqs, dones, ts, texts, finish, prompt_tokens))
+    if (!w_->publish_tokens(conv_ids, token_ids, seqs, dones, ts, texts, finish, prompt_tokens, logprobs))
       throw std::runtime_error("dp worker: token ring closed or full");
     return (int)n;
   }
@@ -358,7 +361,7 @@ PYBIND11_MODULE(_dsse_runtime, m) {
       .def("publish_tokens", &Runtime::publish_tokens, py::arg("conversation_ids"), py::arg("token_ids"),
            py::arg("sequences"), py::arg("dones"), py::arg("timestamp_ns") = 0,
            py::arg("texts") = std::vector<std::string>{}, py::arg("finish") = std::vector<int>{},
-           py::arg("prompt_tokens") = std::vector<int>{})
+           py::arg("prompt_tokens") = std::vector<int>{}, py::arg("logprobs") = std::vector<std::string>{})
       .def("publish", &Runtime::publish, py::arg("conversation_id"), py::arg("token"), py::arg("sequence"),
            py::arg("done") = false, py::arg("timestamp_ns") = 0)
       .def("pop_cancellations", &Runtime::pop_cancellations)
@@ -384,7 +387,7 @@ PYBIND11_MODULE(_dsse_runtime, m) {
       .def("publish_tokens", &DpWorkerPy::publish_tokens, py::arg("conversation_ids"), py::arg("token_ids"),
            py::arg("sequences"), py::arg("dones"), py::arg("timestamp_ns") = 0,
            py::arg("texts") = std::vector<std::string>{}, py::arg("finish") = std::vector<int>{},
-           py::arg("prompt_tokens") = std::vector<int>{})
+           py::arg("prompt_tokens") = std::vector<int>{}, py::arg("logprobs") = std::vector<std::string>{})
       .def("set_ready", &DpWorkerPy::set_ready)
       .def("observe", &DpWorkerPy::observe, py::arg("step_s"), py::arg("batch"), py::arg("kv_free"), py::arg("active"),
            py::arg("ttft"), py::arg("itl"), py::arg("host") = std::vector<double>{})

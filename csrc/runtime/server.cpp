@@ -383,6 +383,9 @@ struct Conn {
   bool openai = false;
   bool oa_stream = true;
   std::string oa_model, oa_text;
+  std::string oa_logprobs;  // non-stream completion with logprobs: the entries so far, comma-separated
+  bool oa_want_logprobs = false;
+  bool oa_lp_missing = false;  // a counted token came without an entry (stub / relay edge / replaced by the gate)
   int64_t oa_created = 0;
   int oa_count = 0, oa_max_tokens = -1;
   // RESP
@@ -846,6 +849,24 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
     auto ie = o.find("ignore_eos");
     r.ignore_eos = ie != o.end() && ie->second.kind == JsonValue::kBool && ie->second.b;
   }
+  {
+    // logprobs: bool; top_logprobs: an integer in [0, 20], only with logprobs: true.  The queued request carries
+    // -1 (off) or N.
+    // A JSON null is "not given" (clients that serialise unset optionals; vLLM reads it the same way).
+    auto lp = o.find("logprobs"), tl = o.find("top_logprobs");
+    if (lp != o.end() && lp->second.kind == JsonValue::kNull) lp = o.end();
+    if (tl != o.end() && tl->second.kind == JsonValue::kNull) tl = o.end();
+    if (lp != o.end() && lp->second.kind != JsonValue::kBool) return bad(400, "logprobs must be a boolean");
+    const bool want = lp != o.end() && lp->second.b;
+    int top = 0;
+    if (tl != o.end()) {
+      const double v = tl->second.kind == JsonValue::kNumber ? tl->second.num : NAN;
+      if (!(v >= 0 && v <= 20) || v != std::floor(v)) return bad(400, "top_logprobs must be an integer in [0, 20]");
+      if (!want) return bad(400, "top_logprobs requires logprobs to be true");
+      top = (int)v;
+    }
+    r.logprobs = want ? top : -1;
+  }
   r.from_edge = true;
   auto mo = o.find("model");
   c.openai = true;
@@ -855,6 +876,9 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   c.oa_count = 0;
   c.oa_max_tokens = r.max_tokens;
   c.oa_text.clear();
+  c.oa_logprobs.clear();
+  c.oa_lp_missing = false;
+  c.oa_want_logprobs = r.logprobs >= 0;
   // subscribe before submitting, as POST /chat does
   auto sink = std::make_shared<ConnSink>();
   sink->io = this;
@@ -900,8 +924,15 @@ void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
   c.got_first = true;
   ++c.oa_count;
   metrics().sse_messages_delivered_total.inc();
+  const bool has_lp = c.oa_want_logprobs && !f->logprobs.empty();
   if (!c.oa_stream) {
     c.oa_text += m.token;
+    if (has_lp) {
+      if (!c.oa_logprobs.empty()) c.oa_logprobs += ',';
+      c.oa_logprobs += f->logprobs;
+    } else {
+      c.oa_lp_missing = true;
+    }
     return;
   }
   const size_t pend = c.out.size() - c.out_off;
@@ -915,7 +946,8 @@ void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
   json_append_string(ev, c.oa_model);
   ev += ",\"choices\":[{\"index\":0,\"delta\":{\"content\":";
   json_append_string(ev, m.token);
-  ev += "},\"logprobs\":null,\"finish_reason\":null}]}\n\n";
+  if (has_lp) ev += "},\"logprobs\":{\"content\":[" + f->logprobs + "]},\"finish_reason\":null}]}\n\n";
+  else ev += "},\"logprobs\":null,\"finish_reason\":null}]}\n\n";
   write_sse_bytes(c, ev);
 }
 
@@ -936,12 +968,18 @@ void IoThread::finish_openai(Conn& c, const char* finish_reason, int prompt_toke
   }
   const bool ka = c.keep_alive;
   std::string body = head + "\"message\":{\"role\":\"assistant\",\"content\":" + json_quote(c.oa_text) +
-                     ",\"tool_calls\":[]},\"logprobs\":null,\"finish_reason\":\"" + finish_reason +
+                     ",\"tool_calls\":[]},\"logprobs\":" +
+                     // one entry per completion token or none at all: a token without one (the stub generator, an
+                     // engine behind a relay edge, a frame the inspection gate replaced) leaves null, as the stream does
+                     (c.oa_want_logprobs && !c.oa_lp_missing && !c.oa_logprobs.empty()
+                          ? "{\"content\":[" + c.oa_logprobs + "]}" : std::string("null")) +
+                     ",\"finish_reason\":\"" + finish_reason +
                      "\",\"stop_reason\":null}]," + usage + "}";
   // buffered mode never wrote headers: close the pseudo-SSE session, then send one JSON response (and close
   // the connection after it when the client asked for Connection: close)
   end_sse(c, false);
   c.oa_text.clear();
+  c.oa_logprobs.clear();
   write_raw(c, simple_response(200, body, "application/json", ka));
   if (!ka) {
     c.close_after_write = true;
@@ -1759,6 +1797,8 @@ FramePtr with_token(const FramePtr& f, const std::string& token) {
   m.token = token;
   m.finish = f->finish;
   m.prompt_tokens = f->prompt_tokens;
+  // (the logprobs entry is NOT carried over: it names the original piece, its bytes and the alternatives, which is
+  // what the inspector hid; a replaced token reports no logprobs)
   return Bus::make_frame(m);
 }
 }  // namespace

@@ -88,6 +88,7 @@ struct ChatRequest {
   double presence_penalty = 0;    // [-2, 2]; these three default to "no penalty"
   double frequency_penalty = 0;   // [-2, 2]
   double repetition_penalty = 1;  // (0, 2]
+  int logprobs = -1;              // OpenAI route: -1 = off, 0..20 = top_logprobs of a request with logprobs: true
   bool from_edge = false;   // submitted by the edge /chat (a subscriber exists)
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON
   // [{"role":..,"content":..},..]; empty = `message` is a single user turn

@@ -68,6 +68,10 @@ class SamplingParams:
     frequency_penalty: float = 0.0   # x[v] -= f * c[v]
     repetition_penalty: float = 1.0  # v in the prompt or generated: x[v] = x[v] / r if x[v] > 0 else x[v] * r
 
+    # raw logprobs (x - logsumexp(x) of the logits before penalties / temperature / filters) of every sampled token
+    # and of the top N tokens: -1 = off, 0..20 = N (sampler.hip logprob_stats_kernel / logprob_finish_kernel)
+    logprobs: int = -1
+
     def penalised(self) -> bool:
         return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
 
@@ -85,6 +89,8 @@ class TokenEvent:
     timestamp_ns: int = 0
     finish: str = ""        # terminal events: "stop" (EOS), "length" (max_tokens / context), "abort"
     prompt_tokens: int = -1  # terminal events: prompt length (OpenAI usage)
+    logprob: float | None = None  # streams that asked for logprobs: the sampled token's raw logprob ...
+    top: list | None = None       # ... and the top N as [(token id, logprob)], logit descending, ties by ascending id
 
 
 @dataclass
@@ -144,19 +150,38 @@ class _Drain:
         if self.cuda:
             self.pf_host = self.pf_host.pin_memory()
             self.pf_events = [torch.cuda.Event() for _ in range(RING_SIZE)]
+        self.lp_host = self.pf_lp_host = None  # host rows of the runner's lp_ring, once logprobs are in use
+
+    def _lp_hosts(self):
+        if self.lp_host is None:
+            shape = (RING_SIZE,) + tuple(self.r.lp_ring.shape[1:])
+            self.lp_host, self.pf_lp_host = torch.zeros(shape), torch.zeros(shape)
+            if self.cuda:
+                self.lp_host, self.pf_lp_host = self.lp_host.pin_memory(), self.pf_lp_host.pin_memory()
+        return self.lp_host, self.pf_lp_host
 
     def issue(self, row: int, width: int, first: bool = False):
         host = self.pf_host if first else self.host
         health = self.pf_health if first else self.health
+        # the logprob rows ride along (same stream, same event, the drained width) once a request has asked for them
+        lp = self._lp_hosts()[1 if first else 0] if self.r.lp_used else None
         if not self.cuda:
             host[row, :width] = self.r.ring[row, :width]
             health[row].copy_(self.r.health)
+            if lp is not None:
+                lp[row, :width] = self.r.lp_ring[row, :width]
             return
         self.stream.wait_stream(torch.cuda.current_stream(self.r.device))
         with torch.cuda.stream(self.stream):
             host[row, :width].copy_(self.r.ring[row, :width], non_blocking=True)
             health[row].copy_(self.r.health, non_blocking=True)
+            if lp is not None:
+                lp[row, :width].copy_(self.r.lp_ring[row, :width], non_blocking=True)
             (self.pf_events if first else self.events)[row].record(self.stream)
+
+    def logprobs(self, row: int, first: bool = False):
+        """Host copy of lp_ring[row] (after wait()), or None while no request has asked for logprobs."""
+        return None if self.lp_host is None else (self.pf_lp_host if first else self.lp_host)[row]
 
     def faults(self, row: int, first: bool = False) -> list:
         """Health faults recorded with ring row `row` (after wait())."""
@@ -302,6 +327,7 @@ class LLMEngine:
         self._rid = itertools.count(1)
         self._dirty_slots: set = set()
         self._pen_live = False  # the device's penalty block holds a non-neutral slot (then _upload rewrites it)
+        self._lp_live = False   # the device's lp_meta holds a slot that is on (likewise)
         self.ring_head = int(runner.ring_counter.item()) if runner.device.type == "cuda" else int(runner.ring_counter[0])
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0}
@@ -455,6 +481,14 @@ class LLMEngine:
                 pf[i], pf[Bm + i], pf[2 * Bm + i] = p.presence_penalty, p.frequency_penalty, p.repetition_penalty
                 pen[3 * Bm + i] = s.orig_len
             self._pen_live = bool(live)
+        # lp_meta (-1 = off, else N): likewise only while a sequence with logprobs holds a slot, and once after
+        lpm = None
+        live = [(i, s) for i, s in enumerate(self.slots) if s is not None and s.params.logprobs >= 0]
+        if live or self._lp_live:
+            lpm = np.full(Bm, -1, dtype=np.int32)
+            for i, s in live:
+                lpm[i] = min(int(s.params.logprobs), 20)
+            self._lp_live = bool(live)
         bt_rows = {}
         for i in self._dirty_slots:
             s = self.slots[i]
@@ -473,6 +507,8 @@ class LLMEngine:
         put(r.slot_meta, torch.from_numpy(meta))
         if pen is not None:
             put(r.pen_meta, torch.from_numpy(pen))
+        if lpm is not None:
+            put(r.lp_meta, torch.from_numpy(lpm))
         for i, row in bt_rows.items():
             put(r.block_tables[i], row)
         self._dirty_slots.clear()
@@ -566,6 +602,8 @@ class LLMEngine:
                 # its history: the prompt as submitted, then (after a preemption) everything it has published
                 # (`prompt` is exactly that); the device appends every token sampled from here on
                 r.set_history(s.slot, s.prompt, s.orig_len)
+            if s.params.logprobs >= 0:
+                r.enable_logprobs()  # (the first such request captures the graph twins with the logprob passes)
 
     def _compact(self):
         """Move decoding sequences above the bucket their count needs into lower free / paused slots."""
@@ -811,7 +849,7 @@ class LLMEngine:
             t_done = time.perf_counter()
             wait += t_done - tw
             self.inflight.popleft()
-            self._consume(toks, prods, events)
+            self._consume(toks, prods, events, self.drain.logprobs(rrow, first))
         # the newest step started when its predecessor finished (the wait above) or, on an idle GPU, when enqueued
         if ran:
             self._jit = (max(t_enq, t_done), est_ms) if n_main == 1 and t_done is not None else (t_enq, est_ms)
@@ -827,9 +865,10 @@ class LLMEngine:
         self.stats["host_s"] = dt - wait
         return events
 
-    def _consume(self, toks, prods, events):
+    def _consume(self, toks, prods, events, lps=None):
         now = time.time_ns()
         tl = toks.tolist()
+        lp_ids = lps.view(torch.int32) if lps is not None else None
         for slot, s in prods:
             if s.state == "finished" or s.state == "preempted" or s.aborted:
                 continue
@@ -846,7 +885,13 @@ class LLMEngine:
             s.last_token_ns = now
             is_eos = tok == self.eos_id and not s.params.ignore_eos
             if not is_eos:
-                events.append(TokenEvent(s.conversation_id, tok, s.produced, False, timestamp_ns=now))
+                ev = TokenEvent(s.conversation_id, tok, s.produced, False, timestamp_ns=now)
+                if s.params.logprobs >= 0 and lps is not None:
+                    n = min(int(s.params.logprobs), 20)
+                    row, ids = lps[slot].tolist(), lp_ids[slot, 1:1 + n].tolist()
+                    ev.logprob = row[0]
+                    ev.top = [(t, row[21 + j]) for j, t in enumerate(ids) if t >= 0]
+                events.append(ev)
                 s.out_ids.append(tok)
                 self.stats["tokens"] += 1
             else:

@@ -242,6 +242,13 @@ class ModelRunner:
         self.hist_used = False  # a history was ever uploaded (move_slots then moves the rows too)
         self.ring = torch.zeros(RING_SIZE, Bm, **i32)
         self.ring_counter = torch.zeros(1, **i32)
+        # logprobs / top_logprobs (sampler.hip logprob_*_kernel): lp_meta[slot] = -1 (off) or N in 0..20, host-owned
+        # and uploaded like slot_meta; lp_ring[ring row, slot] = [logprob of the sampled token | 20 ids | 20 logprobs]
+        # is written where the token itself goes and drained with it (LLMEngine._Drain)
+        self.lp_meta = torch.full((Bm,), -1, **i32)
+        self.lp_ring = torch.zeros(RING_SIZE, Bm, ops.LP_OUT, device=dev, dtype=torch.float32)
+        self.lp_used = False  # a request ever asked for logprobs (then the passes are launched / captured)
+        self._lp_raw = None   # [rows, V] raw copy of the logprob rows, allocated once penalties AND logprobs are in use
         # ---- decode activations ----
         bf = dict(device=dev, dtype=torch.bfloat16)
         self.resid = torch.zeros(Bm, H, device=dev, dtype=torch.float32)
@@ -262,6 +269,9 @@ class ModelRunner:
         self._cand = {b: torch.zeros(b, nch, 2, device=dev, dtype=torch.float32) for b in batch_buckets(Bm)}
         self._cand_all = {b: torch.zeros(self.comm.size, b, nch, 2, device=dev, dtype=torch.float32)
                           for b in batch_buckets(Bm)}
+        self._lp_bufs = {b: self._lp_alloc(b) for b in batch_buckets(Bm)}
+        self._lp_pf = self._lp_alloc(PREFILL_GRAPH_SEQS)
+        self._lp_eager = None  # the eager first-token path's buffers (max_batch rows, allocated at its first use)
         part, nparts = decode_partitioning(1, nkv, max_model_len)
         ws = max(decode_partitioning(b, nkv, max_model_len)[1] * b for b in batch_buckets(Bm))
         self.part_o = torch.zeros(max(1, ws) * nkv * 16 * 128, device=dev, dtype=torch.float32)
@@ -279,9 +289,11 @@ class ModelRunner:
         self.pf_graphs = {}   # row bucket -> captured prefill graph
         self.pf = None        # static prefill buffers (allocated by capture)
         self.mx_graphs = {}   # decode bucket B -> [(chunk rows C, captured mixed prefill + decode graph)], C ascending
-        # their twins with the penalty pass, captured at the first penalised request (_capture_penalty_graphs)
+        # their twins per (penalties used, logprobs used), each captured the first time that combination is needed
+        # (_capture_twins); pen_* = the (True, False) set: the penalty pass and nothing else new
         self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs = {}, {}, {}
-        self._graphs_have_pass = False  # capture() ran after penalties were already in use: one set, with the pass
+        self._twins = {(True, False): (self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs)}
+        self._captured_key = (False, False)  # the passes the graphs of capture() hold (set there)
         self.host_trace = None  # a list: host seconds of each graph-replayed mixed step (upload, replay, sampling)
 
     # ------------------------------------------------------------------ decode
@@ -369,6 +381,9 @@ class ModelRunner:
         cand = self._cand[B]
         # penalties first (rows with neutral parameters return at once); the pick appends to the penalised histories.
         # The pass is launched (and captured: _capture_penalty_graphs) only once a request has asked for penalties
+        # logprob statistics before them: the penalty pass rewrites logits in place (same lazy launch / capture)
+        if self.lp_used:
+            raw = self._logprob_stats(self.logits[r], self.active[r], None, self._lp_bufs[B])
         if self.hist_used:
             ops.sample_penalties(self.logits[r], self.active[r], self.pen_meta, self.hist_state, None,
                                  self.w.vocab_offset, self.cfg.vocab_size)
@@ -381,6 +396,58 @@ class ModelRunner:
             self.comm.all_gather_into(cand_all, cand)
         ops.sample_pick_hist(cand_all, self.active[r], self.ids[r], self.ring, self.ring_counter, self.positions[r],
                              self.pen_meta, self.hist_state, vocab=self.cfg.vocab_size)
+        if self.lp_used:  # (before ring_advance: the same ring row the pick wrote)
+            self._logprob_finish(self.logits[r], raw, self.ids[r], self.active[r], None, self._lp_bufs[B],
+                                 ring_counter=self.ring_counter)
+
+    # ------------------------------------------------------------------ logprobs
+    def _lp_alloc(self, n: int) -> dict:
+        """Record / chosen-logit buffers of an n-row sampling site (and their all-gathered forms under TP)."""
+        f32 = dict(device=self.device, dtype=torch.float32)
+        d = dict(rec=torch.zeros(n, ops.LP_REC, **f32), chosen=torch.zeros(n, **f32))
+        if self.comm.size > 1:
+            d.update(rec_all=torch.zeros(self.comm.size, n, ops.LP_REC, **f32),
+                     chosen_all=torch.zeros(self.comm.size, n, **f32))
+        return d
+
+    def _lp_eager_bufs(self, n: int) -> dict:
+        """Buffers of an n-row eager first-token sampling (n <= max_batch): contiguous views of one cached set."""
+        if self._lp_eager is None:
+            self._lp_eager = {k: v.view(-1) for k, v in self._lp_alloc(self.max_batch).items()}
+        e, W = self._lp_eager, self.comm.size
+        d = dict(rec=e["rec"][:n * ops.LP_REC].view(n, ops.LP_REC), chosen=e["chosen"][:n])
+        if W > 1:
+            d.update(rec_all=e["rec_all"][:W * n * ops.LP_REC].view(W, n, ops.LP_REC),
+                     chosen_all=e["chosen_all"][:W * n].view(W, n))
+        return d
+
+    def _logprob_stats(self, logits, active, row_slot, bufs):
+        """Per-rank (max, sum, top-N) records of the rows whose slot has logprobs on, from the logits as the LM head
+        wrote them.  Returns the raw copy of those rows when a penalty pass follows (else None)."""
+        raw = self._lp_raw[:logits.shape[0]] if self.hist_used else None
+        ops.logprob_stats(logits, active, self.lp_meta, row_slot, bufs["rec"], raw, self.w.vocab_offset)
+        return raw
+
+    def _logprob_finish(self, logits, raw, ids, active, row_slot, bufs, **ring) -> None:
+        """After the pick / commit: this shard's raw logit of each sampled token, (TP: the records and those 4 B per
+        row all-gathered,) then the merge into lp_ring at the token's own (ring row, slot)."""
+        ops.logprob_chosen(logits if raw is None else raw, ids, active, self.lp_meta, row_slot, bufs["chosen"],
+                           self.w.vocab_offset, self.cfg.vocab_size)
+        if self.comm.size == 1:
+            rec_all, chosen_all = bufs["rec"].unsqueeze(0), bufs["chosen"].unsqueeze(0)
+        else:
+            rec_all, chosen_all = bufs["rec_all"], bufs["chosen_all"]
+            self.comm.all_gather_into(rec_all, bufs["rec"])
+            self.comm.all_gather_into(chosen_all, bufs["chosen"])
+        ops.logprob_finish(rec_all, chosen_all, active, self.lp_meta, row_slot, self.lp_ring,
+                           vocab=self.cfg.vocab_size, **ring)
+
+    def enable_logprobs(self) -> None:
+        """The first request with logprobs: from now on every sampling site runs the logprob passes (rows whose slot
+        is off return at once) and the graph twins that hold them are replayed."""
+        if not self.lp_used:
+            self.lp_used = True
+            self._capture_twins()
 
     def set_history(self, slot: int, tokens: list, n_prompt: int) -> None:
         """A penalised sequence takes `slot`: its tokens so far (the submitted prompt, then what it has published)
@@ -394,45 +461,59 @@ class ModelRunner:
         self.hist_state[slot, :row.numel()].copy_(row, non_blocking=True)
         if not self.hist_used:
             self.hist_used = True
-            self._capture_penalty_graphs()
+            self._capture_twins()
 
-    def _capture_penalty_graphs(self) -> None:
-        """The first penalised request: every captured graph gets a twin with the penalty pass in front of the
-        candidates (one more launch per sampled step), replayed from now on; until then the graphs captured at
-        startup run, which hold no such launch (an early-exit launch per step measured +8 us on the 4.23 ms
-        64-stream step: profiles/r7/penalties.md).  Stream capture executes nothing, so no decode state changes;
-        the shapes, buffers and collectives are the ones the startup capture warmed.  Deterministic across a TP
-        group: every rank admits the same request in the same step."""
-        if self._graphs_have_pass or not (self.graphs or self.pf_graphs or self.mx_graphs):
+    def _capture_twins(self) -> None:
+        """The first request that needs a new combination of (penalties, logprobs): every captured graph gets a twin
+        with the penalty pass in front of the candidates and / or the logprob passes around them, replayed from now
+        on; until then the graphs captured at startup run, which hold no such launch and no extra collective (an
+        early-exit launch per step measured +8 us on the 4.23 ms 64-stream step: profiles/r7/penalties.md).  At most
+        three such captures in a process's life.  Stream capture executes nothing, so no decode state changes; the
+        shapes and buffers are the ones the startup capture warmed, and the logprob all-gathers run once eagerly
+        first.  Deterministic across a TP group: every rank admits the same request in the same step."""
+        key = (self.hist_used, self.lp_used)
+        if key == (True, True) and self._lp_raw is None:
+            self._lp_raw = torch.zeros(max(self.max_batch, PREFILL_GRAPH_SEQS), self.w.vocab_local,
+                                       device=self.device, dtype=torch.float32)
+        if key == self._captured_key or any(self._twins.get(key, ())) or \
+                not (self.graphs or self.pf_graphs or self.mx_graphs):
             return
+        dec, pfg, mxg = self._twins.setdefault(key, ({}, {}, {}))
+        if self.lp_used and self.comm.size > 1:
+            for bufs in (self._lp_bufs[max(self._lp_bufs)], self._lp_pf):
+                self.comm.all_gather_into(bufs["rec_all"], bufs["rec"])
+                self.comm.all_gather_into(bufs["chosen_all"], bufs["chosen"])
         t0 = time.perf_counter()
         for B in sorted(self.graphs, reverse=True):
             g = torch.cuda.CUDAGraph()
             with _capture(g, pool=self.graph_pool):
                 self.decode_forward(B)
-            self.pen_graphs[B] = g
+            dec[B] = g
         for tb in sorted(self.pf_graphs, reverse=True):
             g = torch.cuda.CUDAGraph()
             with _capture(g, pool=self.graph_pool):
                 self._prefill_layers(tb, self.pf.views(tb))
                 self._graph_sample()
-            self.pen_pf_graphs[tb] = g
+            pfg[tb] = g
         for B, C in sorted(((B, C) for B, lst in self.mx_graphs.items() for C, _ in lst), reverse=True):
             g = torch.cuda.CUDAGraph()
             with _capture(g, pool=self.graph_pool):
                 self._mixed_layers(B, C)
                 self._graph_sample()
-            self.pen_mx_graphs.setdefault(B, []).insert(0, (C, g))
+            mxg.setdefault(B, []).insert(0, (C, g))
         torch.cuda.synchronize(self.device)
+        self.twin_capture_s = time.perf_counter() - t0
         if self.comm.rank == 0:
-            print(f"[engine] first penalised request: captured the graphs with the penalty pass "
-                  f"({time.perf_counter() - t0:.2f} s)", flush=True)
+            what = " and ".join(n for n, on in zip(("the penalty pass", "the logprob passes"), key) if on)
+            print(f"[engine] first request with this combination: captured the graphs with {what} "
+                  f"({self.twin_capture_s:.2f} s)", flush=True)
 
     def _graph_set(self):
-        """(decode, prefill, mixed) graphs to replay: the twins with the penalty pass once penalties are in use."""
-        if self.hist_used and not self._graphs_have_pass:
-            return self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs
-        return self.graphs, self.pf_graphs, self.mx_graphs
+        """(decode, prefill, mixed) graphs to replay: the twins that hold the passes in use (penalties, logprobs)."""
+        key = (self.hist_used, self.lp_used)
+        if key == self._captured_key:
+            return self.graphs, self.pf_graphs, self.mx_graphs
+        return self._twins.get(key) or ({}, {}, {})
 
     def health_faults(self, words) -> list:
         """Descriptions of the nonzero health words in `words` (a host copy of self.health)."""
@@ -510,7 +591,10 @@ class ModelRunner:
         Neither: eager decode (reason logged)."""
         if not self.use_graphs:
             return
-        self._graphs_have_pass = self.hist_used
+        self._captured_key = (self.hist_used, self.lp_used)
+        for twins in self._twins.values():  # recorded against the previous capture's graphs and buffers
+            for d in twins:
+                d.clear()
         prefill_graphs = True
         if self.comm.size > 1:
             ipc = self.ipc_decode()
@@ -642,7 +726,8 @@ class ModelRunner:
             idx = idx.pin_memory().to(self.device, non_blocking=True)
         si, di = idx[0], idx[1]
         # the token histories (length word + tokens) travel with their slots once any sequence has used penalties
-        for t in (self.ids, self.positions) + ((self.hist_state,) if self.hist_used else ()):
+        for t in (self.ids, self.positions) + ((self.hist_state,) if self.hist_used else ()) + \
+                ((self.lp_meta,) if self.lp_used else ()):
             t.index_copy_(0, di, t.index_select(0, si))
 
     def decode(self, B: int) -> None:
@@ -845,8 +930,11 @@ class ModelRunner:
         sd = self.seeds.index_select(0, slot_idx).contiguous()
         nch = SAMPLE_CHUNKS if dev.type == "cuda" else 1
         cand = torch.zeros(nL, nch, 2, **f32)
-        if self.hist_used:  # (an eager pass: nothing is launched until a request has asked for penalties)
-            slot_i32 = slot_idx.to(torch.int32)
+        slot_i32 = slot_idx.to(torch.int32) if self.hist_used or self.lp_used else None
+        if self.lp_used:  # (eager passes: nothing is launched until a request has asked for logprobs / penalties)
+            lp_bufs = self._lp_eager_bufs(nL)
+            raw = self._logprob_stats(logits, None, slot_i32, lp_bufs)
+        if self.hist_used:
             # after a re-prefill the tokens already published count: the engine uploaded them with the history
             ops.sample_penalties(logits, None, self.pen_meta, self.hist_state, slot_i32, w.vocab_offset,
                                  cfg.vocab_size)
@@ -859,6 +947,8 @@ class ModelRunner:
         ops.sample_pick(cand_all, None, new_ids, vocab=cfg.vocab_size)
         if self.hist_used:
             ops.sample_hist_append(new_ids, slot_i32, None, self.pen_meta, self.hist_state)
+        if self.lp_used:
+            self._logprob_finish(logits, raw, new_ids, None, slot_i32, lp_bufs, ring_row=ring_row)
         self.ids.index_copy_(0, slot_idx, new_ids)
         self.ring[ring_row].index_copy_(0, slot_idx, new_ids)
         self.positions.index_copy_(0, slot_idx, last_pos + 1)
@@ -927,6 +1017,8 @@ class ModelRunner:
         ops.prefill_sample_gather(pf.x, meta, self.slot_meta, pf.s_xl, sm)
         ops.gemm_out(pf.s_xl, w.lm_head_t, pf.s_logits)
         active = sm[:ns]
+        if self.lp_used:
+            raw = self._logprob_stats(pf.s_logits, active, meta[ns:2 * ns], self._lp_pf)
         if self.hist_used:  # gathered row i samples for slot meta[ns + i]: its penalties and history
             ops.sample_penalties(pf.s_logits, active, self.pen_meta, self.hist_state, meta[ns:2 * ns],
                                  w.vocab_offset, cfg.vocab_size)
@@ -941,6 +1033,9 @@ class ModelRunner:
         ops.sample_pick(cand_all, active, pf.s_new, vocab=cfg.vocab_size)
         ops.prefill_sample_commit_hist(meta, pf.s_new, self.ids, self.ring, self.positions, self.pen_meta,
                                        self.hist_state)
+        if self.lp_used:
+            self._logprob_finish(pf.s_logits, raw, pf.s_new, active, meta[ns:2 * ns], self._lp_pf,
+                                 ring_row_dev=meta[3 * ns + 1:3 * ns + 2])
 
     def mixed(self, B: int, seqs: list, ring_row: int) -> None:
         """ONE forward over the decode slots [0, B) and the prefill chunks `seqs` (rows B .. B+T-1): every weight

@@ -284,6 +284,45 @@ def sample_hist_append(new_ids, row_slot, active, pen_meta, hist):
         ref.sample_hist_append(new_ids, row_slot, active, pen_meta, hist)
 
 
+LP_TOP = 20            # top_logprobs at most
+LP_REC = 2 + 2 * LP_TOP   # per-(rank, row) record [max | sum exp(x - max) | LP_TOP x (logit, id bits)]
+LP_OUT = 1 + 2 * LP_TOP   # per-token result [logprob of the sampled token | LP_TOP ids | LP_TOP logprobs]
+
+
+def logprob_stats(logits, active, lp_meta, row_slot, rec, raw=None, vocab_offset=0):
+    """Raw-logprob statistics of this rank's logits shard [B, V] (fp32, as the LM head wrote them: call it BEFORE
+    sample_penalties).  lp_meta int32 [slots]: -1 = off, 0..20 = N; row b is slot row_slot[b] (else b).  Rows that
+    are active and on get rec[b] = [max | sum exp(x - max) | 20 x (logit, global id bits)]: the shard's top-N by
+    logit descending, equal logits by ascending id, unused entries (-inf, 0x7fffffff); `raw` [>= B, V] (optional)
+    receives a copy of those rows.  Other rows leave rec / raw untouched."""
+    if _hip(logits):
+        torch.ops.dsse.logprob_stats(logits, active, lp_meta, row_slot, rec, raw, vocab_offset)
+    else:
+        ref.logprob_stats(logits, active, lp_meta, row_slot, rec, raw, vocab_offset)
+
+
+def logprob_chosen(logits, next_ids, active, lp_meta, row_slot, chosen, vocab_offset=0, vocab: int = 2**31 - 1):
+    """chosen[b] = logits[b, next_ids[b] - vocab_offset] when this shard holds the sampled id, else -inf (rows that
+    are active and on).  `logits` must be the un-penalised values (logprob_stats' raw copy after a penalty pass)."""
+    if _hip(logits):
+        torch.ops.dsse.logprob_chosen(logits, next_ids, active, lp_meta, row_slot, chosen, vocab_offset, vocab)
+    else:
+        ref.logprob_chosen(logits, next_ids, active, lp_meta, row_slot, chosen, vocab_offset, vocab)
+
+
+def logprob_finish(rec_all, chosen_all, active, lp_meta, row_slot, lp_ring, ring_counter=None, ring_row_dev=None,
+                   ring_row: int = -1, vocab: int = 2**31 - 1):
+    """Merge rec_all [world, B, 42] and chosen_all [world, B]: lse over all shards, the global top-N in the same
+    order, and lp_ring[row, slot] = [logprob of the sampled token | 20 ids | 20 logprobs] (entries past min(N, vocab):
+    id -1, -inf).  row = ring_counter[0] % R, else ring_row_dev[0], else ring_row: where the token itself went."""
+    if _hip(rec_all):
+        torch.ops.dsse.logprob_finish(rec_all, chosen_all, active, lp_meta, row_slot, lp_ring, ring_counter,
+                                      ring_row_dev, ring_row, vocab)
+    else:
+        ref.logprob_finish(rec_all, chosen_all, active, lp_meta, row_slot, lp_ring, ring_counter, ring_row_dev,
+                           ring_row, vocab)
+
+
 def sample(logits, temperature, top_k, top_p, seeds, positions, active, next_ids, ring=None, ring_counter=None,
            positions_inc=None, nchunks: int = 16):
     """Single-rank convenience: candidates + pick."""

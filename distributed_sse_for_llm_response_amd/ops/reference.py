@@ -418,3 +418,89 @@ def prefill_sample_commit_hist(meta, new_ids, ids, ring, positions, pen_meta, hi
     NS = new_ids.numel()
     for i in range(min(int(meta[3 * NS]), NS)):
         _hist_append(pen_meta, hist, int(meta[NS + i]), int(new_ids[i]))
+
+
+# ---- logprobs / top_logprobs (sampler.hip logprob_stats_kernel / logprob_chosen_kernel / logprob_finish_kernel) ----
+# Raw logprobs: x[v] - logsumexp(x) over the full vocabulary of the fp32 logits as the LM head wrote them.  lp_meta
+# int32 [slots]: -1 = off, 0..LP_TOP = N.  Order of the top-N: logit descending, equal logits by ascending global id.
+LP_TOP = 20
+LP_REC = 2 + 2 * LP_TOP
+LP_OUT = 1 + 2 * LP_TOP
+_LP_NONE = 0x7FFFFFFF
+_NEG_INF = float("-inf")
+
+
+def _lp_row(active, lp_meta, row_slot, b: int):
+    """(N, slot) of row b; N < 0: the row is inactive or off."""
+    if active is not None and not int(active[b]):
+        return -1, -1
+    slot = int(row_slot[b]) if row_slot is not None else b
+    return min(int(lp_meta[slot]), LP_TOP), slot
+
+
+def logprob_stats(logits, active, lp_meta, row_slot, rec, raw=None, vocab_offset=0):
+    B, V = logits.shape
+    rec_i = rec.view(torch.int32)
+    for b in range(B):
+        N, _ = _lp_row(active, lp_meta, row_slot, b)
+        if N < 0:
+            continue
+        x = logits[b].to(torch.float32)
+        if raw is not None:
+            raw[b].copy_(x)
+        m = x.max()
+        rec[b, 0] = m
+        rec[b, 1] = torch.exp(x - m).sum() if float(m) > _NEG_INF else 0.0
+        rec[b, 2::2] = _NEG_INF
+        rec_i[b, 3::2] = _LP_NONE
+        n = min(N, V)
+        if n > 0:
+            vals, idx = torch.sort(x + 0.0, descending=True, stable=True)  # stable: equal logits by ascending id
+            rec[b, 2:2 + 2 * n:2] = vals[:n]
+            rec_i[b, 3:3 + 2 * n:2] = (idx[:n] + vocab_offset).to(torch.int32)
+
+
+def logprob_chosen(logits, next_ids, active, lp_meta, row_slot, chosen, vocab_offset=0, vocab: int = 2**31 - 1):
+    B, V = logits.shape
+    for b in range(B):
+        N, _ = _lp_row(active, lp_meta, row_slot, b)
+        if N < 0:
+            continue
+        v = int(next_ids[b]) - vocab_offset
+        chosen[b] = logits[b, v] if 0 <= v < V else _NEG_INF
+
+
+def logprob_finish(rec_all, chosen_all, active, lp_meta, row_slot, lp_ring, ring_counter=None, ring_row_dev=None,
+                   ring_row: int = -1, vocab: int = 2**31 - 1):
+    world, B = rec_all.shape[0], rec_all.shape[1]
+    R = lp_ring.shape[0]
+    if ring_counter is not None:
+        row = int(ring_counter[0]) % R
+    elif ring_row_dev is not None:
+        row = int(ring_row_dev[0])
+    else:
+        row = int(ring_row)
+    rec_i = rec_all.view(torch.int32)
+    ring_i = lp_ring.view(torch.int32)
+    f32 = torch.float32
+    for b in range(B):
+        N, slot = _lp_row(active, lp_meta, row_slot, b)
+        if N < 0:
+            continue
+        m = rec_all[:, b, 0]
+        M = m.max()
+        s = torch.zeros((), dtype=f32)
+        for w in range(world):  # an empty / all -inf shard (s = 0, m = -inf) adds nothing: no inf - inf
+            if float(m[w]) > _NEG_INF and float(rec_all[w, b, 1]) > 0.0:
+                s = s + rec_all[w, b, 1] * torch.exp(m[w] - M)
+        lse = M + torch.log(s) if float(s) > 0.0 else torch.tensor(_NEG_INF)
+        c = chosen_all[:, b].max()
+        lp_ring[row, slot, 0] = c - lse if float(c) > _NEG_INF else _NEG_INF
+        cand = sorted(((-float(rec_all[w, b, 2 + 2 * j]), int(rec_i[w, b, 3 + 2 * j]), w * LP_TOP + j)
+                       for w in range(world) for j in range(LP_TOP)))
+        for rank in range(LP_TOP):
+            neg, tid, k = cand[rank]
+            used = rank < N and tid != _LP_NONE
+            ring_i[row, slot, 1 + rank] = tid if used else -1
+            val = rec_all[k // LP_TOP, b, 2 + 2 * (k % LP_TOP)]
+            lp_ring[row, slot, 1 + LP_TOP + rank] = val - lse if used and float(val) > _NEG_INF else _NEG_INF

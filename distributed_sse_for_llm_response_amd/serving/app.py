@@ -14,6 +14,7 @@ Engine kinds:
 from __future__ import annotations
 
 import threading
+import json
 import os
 import time
 
@@ -114,7 +115,9 @@ class EngineLoop(threading.Thread):
             # (range-checked by the HTTP server; a request without them carries the neutral values)
             presence_penalty=float(req.get("presence_penalty", d.presence_penalty)),
             frequency_penalty=float(req.get("frequency_penalty", d.frequency_penalty)),
-            repetition_penalty=float(req.get("repetition_penalty", d.repetition_penalty)))
+            repetition_penalty=float(req.get("repetition_penalty", d.repetition_penalty)),
+            # -1 = off, else top_logprobs (0..20) of an OpenAI request with logprobs: true
+            logprobs=int(req.get("logprobs", -1)))
 
     def flow_events(self) -> list:
         """Flow-control transitions from the runtime plus pauses that outlived ``max_pause_s``."""
@@ -136,11 +139,29 @@ class EngineLoop(threading.Thread):
                 return
             self._publish(events)
 
+    def _lp_item(self, token_id: int, logprob: float) -> str:
+        """{"token": piece, "logprob": f, "bytes": [the piece's UTF-8 bytes]} without the closing brace.  %.9g
+        round-trips every fp32; JSON has no -inf: -9999.0, as vLLM writes it."""
+        piece = self.tok.piece(token_id)
+        lp = format(logprob, ".9g") if logprob > -9999.0 else "-9999.0"
+        return f'{{"token":{json.dumps(piece)},"logprob":{lp},"bytes":{json.dumps(list(piece.encode("utf-8")), separators=(",", ":"))}'
+
+    def logprobs_entry(self, e) -> str:
+        """The OpenAI `logprobs.content` entry of a token event that carries logprobs ("" otherwise)."""
+        if e.logprob is None or e.done:
+            return ""
+        tops = ",".join(self._lp_item(t, v) + "}" for t, v in (e.top or ()))
+        return self._lp_item(e.token_id, e.logprob) + f',"top_logprobs":[{tops}]}}'
+
     def _publish(self, events):
-        self.rt.publish_tokens([e.conversation_id for e in events], [e.token_id for e in events],
-                               [e.sequence for e in events], [e.done for e in events], 0,
-                               [e.text for e in events], [FINISH_CODES.get(e.finish, 0) for e in events],
-                               [e.prompt_tokens for e in events])
+        args = ([e.conversation_id for e in events], [e.token_id for e in events],
+                [e.sequence for e in events], [e.done for e in events], 0,
+                [e.text for e in events], [FINISH_CODES.get(e.finish, 0) for e in events],
+                [e.prompt_tokens for e in events])
+        if any(e.logprob is not None for e in events):
+            self.rt.publish_tokens(*args, [self.logprobs_entry(e) for e in events])
+        else:
+            self.rt.publish_tokens(*args)
 
     def tokenize(self, req):
         """Prompt ids of a queued request, or None after publishing a terminal [ERROR] event for it: a

@@ -15,7 +15,7 @@ ring per follower, the follower polls for 2 ms -- longer than a TP decode step -
 microseconds -- ``tools/bench_plan_channel.py``, ``profiles/r3/plan_channel.md``); ``GlooPlanChannel`` (header
 broadcast, then the payload only when there is one) is the fallback when the ranks do not share a node.  The
 leader applies the DECODED plan, exactly what the followers apply, so every rank admits the same parameters
-(seed, float32 temperature / top-p / presence, frequency and repetition penalties).  Followers know sequences by the leader's request id (``Sequence.rid``,
+(seed, float32 temperature / top-p / presence, frequency and repetition penalties, the logprobs count).  Followers know sequences by the leader's request id (``Sequence.rid``,
 which also seeds their sampling), so no conversation-id strings cross ranks.
 
 Reference: the reference configures TP only as a vLLM flag (kubernetes/base/llm/deployment.yaml:88-89).
@@ -69,7 +69,7 @@ class Plan:
                 s_lo, s_hi = sd & 0x7FFFFFFF, (sd >> 31) & 0x7FFFFFFF
             w += [rid, arrival & 0x7FFFFFFF, (arrival >> 31) & 0x7FFFFFFF, int(p.max_tokens), int(p.top_k), s_lo, s_hi,
                   int(bool(p.ignore_eos)), _f2i(p.temperature), _f2i(p.top_p), _f2i(p.presence_penalty),
-                  _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), len(prompt)]
+                  _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), int(p.logprobs), len(prompt)]
             w += [int(t) for t in prompt]
         for rid in self.aborts:
             w.append(rid)
@@ -82,14 +82,14 @@ class Plan:
         p = Plan(step=bool(flags & F_STEP), stop=bool(flags & F_STOP), sync=bool(flags & F_SYNC))
         o = 0
         for _ in range(n_add):
-            rid, a_lo, a_hi, mt, tk, s_lo, s_hi, ie, temp, top_p, pres, freq, rep, n = w[o:o + 14]
-            o += 14
+            rid, a_lo, a_hi, mt, tk, s_lo, s_hi, ie, temp, top_p, pres, freq, rep, lp, n = w[o:o + 15]
+            o += 15
             prompt = w[o:o + n]
             o += n
             sp = SamplingParams(temperature=_i2f(temp), top_p=_i2f(top_p), top_k=tk, max_tokens=mt,
                                 seed=None if s_lo < 0 else s_lo | (s_hi << 31), ignore_eos=bool(ie),
                                 presence_penalty=_i2f(pres), frequency_penalty=_i2f(freq),
-                                repetition_penalty=_i2f(rep))
+                                repetition_penalty=_i2f(rep), logprobs=lp)
             p.adds.append((rid, prompt, sp, a_lo | (a_hi << 31)))
         for _ in range(n_abort):
             p.aborts.append(w[o])
