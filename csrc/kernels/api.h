@@ -110,7 +110,23 @@ struct SampleParams {
   int* hist;                 // [pen_slots, hist_ld]: word 0 = tokens held, then the prompt and the generated tokens
   int hist_ld, pen_slots;
   const int* row_slot;       // [B] slot of logits row b, or null (row b = slot b)
+  // logit_bias / min_tokens / stop_token_ids (sample_bias_ban_kernel) and min_p (sample_filtered_kernel); null =
+  // off, what every launcher without them passes.  All slot-indexed (row b -> slot row_slot[b], else b).
+  const int* ctl_meta;       // [4, ctl_slots]: bias entries | banned ids | ban-until position | min_p (float bits)
+  const int* ctl_body;       // [ctl_slots, kCtlBody]: kCtlBias x (global id, bias float bits), then kCtlBan banned ids
+  int ctl_slots;
+  const float* min_p;        // [ctl_slots] (= ctl_meta's fourth column) or null; <= 0 -> off
 };
+
+// Per-slot record of the bias and ban pass, host-owned.  ctl_meta (uploaded with the slot metadata, neutral = all
+// zero): word [slot] = n_bias in 0..kCtlBias, [ctl_slots + slot] = n_ban in 0..kCtlBan, [2 ctl_slots + slot] =
+// ban_until = prompt length as submitted + min_tokens (the ban is in force while the sampled token's position,
+// positions[b] + 1, is below it), [3 ctl_slots + slot] = min_p.  ctl_body[slot] (uploaded when a sequence that uses
+// it takes the slot): words [2j, 2j + 1] = (global token id, bias as float bits) for j < n_bias, ids distinct; words
+// [2 kCtlBias + j] = banned global id j < n_ban (EOS unless ignore_eos, then the stop_token_ids).
+constexpr int kCtlBias = 300;
+constexpr int kCtlBan = 17;
+constexpr int kCtlBody = 2 * kCtlBias + kCtlBan + 3;  // 620 words (row start 16 B aligned)
 
 // Log-probabilities of the sampled token and the top-N (sampler.hip logprob_*_kernel): raw logprobs, x - logsumexp(x)
 // over the full vocabulary of the fp32 logits as the LM head wrote them (before penalties / temperature / filters).
@@ -163,6 +179,7 @@ hipError_t dsse_prefill_sample_gather(const void* x, int T, int H, const int* me
 hipError_t dsse_prefill_sample_commit(const int* meta, int NS, const int* new_ids, int* ids, int Bm, int* ring, int R,
                                       int* positions, const int* pen_meta, int* hist, int hist_ld, hipStream_t st);
 hipError_t dsse_sample_penalties(int B, float* logits, const dsse::SampleParams* p, hipStream_t st);
+hipError_t dsse_sample_bias_ban(int B, float* logits, const dsse::SampleParams* p, hipStream_t st);
 hipError_t dsse_sample_hist_append(int n, const int* new_ids, const dsse::SampleParams* p, hipStream_t st);
 hipError_t dsse_logprob_stats(int B, const dsse::LogprobParams* p, hipStream_t st);
 hipError_t dsse_logprob_chosen(int B, const dsse::LogprobParams* p, hipStream_t st);

@@ -1104,6 +1104,92 @@ void sample_penalties(Tensor& logits, const c10::optional<Tensor>& active, const
   DSSE_CHECK_HIP(dsse_sample_penalties(B, logits.data_ptr<float>(), &p, cur_stream()));
 }
 
+// ---- logit_bias / min_tokens / stop_token_ids and min_p (sampler.hip sample_bias_ban_kernel, row_min_p) -----------
+// ctl_meta: int32 [4 Bm] = [bias entries | banned ids | ban-until position | min_p (float bits)]; ctl_body: int32
+// [Bm, 620] = [300 x (global id, bias float bits) | 17 banned ids | pad], both slot-indexed (api.h).
+void control_state(dsse::SampleParams& p, const Tensor& ctl_meta, const c10::optional<Tensor>& ctl_body) {
+  check_gpu(ctl_meta, "ctl_meta");
+  check_dtype(ctl_meta, at::kInt, "ctl_meta");
+  TORCH_CHECK(ctl_meta.is_contiguous() && ctl_meta.numel() >= 4 && ctl_meta.numel() % 4 == 0 &&
+                  ctl_meta.numel() / 4 <= INT32_MAX, "ctl_meta must be [4 x slots]");
+  p.ctl_slots = (int)(ctl_meta.numel() / 4);
+  p.ctl_meta = ctl_meta.data_ptr<int>();
+  p.min_p = reinterpret_cast<const float*>(p.ctl_meta + 3 * (size_t)p.ctl_slots);
+  if (ctl_body.has_value()) {
+    check_gpu(*ctl_body, "ctl_body");
+    check_dtype(*ctl_body, at::kInt, "ctl_body");
+    TORCH_CHECK(ctl_body->dim() == 2 && ctl_body->is_contiguous() && ctl_body->size(0) == p.ctl_slots &&
+                    ctl_body->size(1) == dsse::kCtlBody, "ctl_body must be a contiguous [slots, 620]");
+    p.ctl_body = ctl_body->data_ptr<int>();
+  }
+}
+
+void control_rows(dsse::SampleParams& p, const c10::optional<Tensor>& row_slot, int B) {
+  if (row_slot.has_value()) {
+    check_gpu(*row_slot, "row_slot");
+    check_dtype(*row_slot, at::kInt, "row_slot");
+    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
+    p.row_slot = row_slot->data_ptr<int>();
+  } else {
+    TORCH_CHECK(B <= p.ctl_slots, "more rows than slots (no row_slot map)");
+  }
+}
+
+// In place on logits [B, V] (row stride >= V): after logprob_stats, before sample_penalties.  positions [B] = the
+// position of each row's predecessor token (what sample_candidates takes).
+void sample_bias_ban(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& ctl_meta,
+                     const Tensor& ctl_body, const Tensor& positions, const c10::optional<Tensor>& row_slot,
+                     int64_t vocab_offset, int64_t vocab) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");
+  check_dtype(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
+                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
+  const int B = (int)logits.size(0), V = (int)logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= 32768, "sampler supports V <= 32768 per rank");
+  check_gpu(positions, "positions");
+  check_dtype(positions, at::kInt, "positions");
+  TORCH_CHECK(positions.numel() >= B, "positions too short");
+  dsse::SampleParams p{};
+  control_state(p, ctl_meta, ctl_body);
+  control_rows(p, row_slot, B);
+  if (active.has_value()) {
+    check_gpu(*active, "active");
+    check_dtype(*active, at::kInt, "active");
+    TORCH_CHECK(active->numel() >= B, "active too short");
+    p.active = active->data_ptr<int>();
+  }
+  p.positions = positions.data_ptr<int>();
+  p.ld = (int)logits.stride(0);
+  p.V = V;
+  p.vocab_offset = (int)vocab_offset;
+  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
+  DSSE_CHECK_HIP(dsse_sample_bias_ban(B, logits.data_ptr<float>(), &p, cur_stream()));
+}
+
+// sample_candidates with min_p: ctl_meta's fourth column holds min_p per slot (row b = slot row_slot[b], else b).
+void sample_candidates_min_p(const Tensor& logits, const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
+                             const Tensor& seeds, const Tensor& positions, const c10::optional<Tensor>& active,
+                             Tensor& cand, const Tensor& ctl_meta, const c10::optional<Tensor>& row_slot,
+                             int64_t vocab_offset) {
+  check_gpu(logits, "logits");
+  check_dtype(logits, at::kFloat, "logits");
+  check_gpu(cand, "cand");
+  check_dtype(cand, at::kFloat, "cand");
+  const int B = (int)logits.size(0), V = (int)logits.size(1);
+  TORCH_CHECK(V <= 32768, "sampler supports V <= 32768 per rank");
+  TORCH_CHECK(cand.dim() == 3 && cand.size(0) == B && cand.size(2) == 2, "cand must be [B, nchunks, 2]");
+  dsse::SampleParams p = sample_params(temperature, top_k, top_p, seeds, positions, active, B);
+  control_state(p, ctl_meta, c10::nullopt);
+  control_rows(p, row_slot, B);
+  p.logits = logits.data_ptr<float>();
+  p.ld = V;
+  p.V = V;
+  p.vocab_offset = (int)vocab_offset;
+  p.cand = reinterpret_cast<float2*>(cand.data_ptr<float>());
+  p.nchunks = (int)cand.size(1);
+  DSSE_CHECK_HIP(dsse_sample(B, &p, cur_stream()));
+}
+
 // sample_pick whose picked token also joins hist[b] where slot b has penalties on.
 void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
                       const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
@@ -1534,6 +1620,11 @@ TORCH_LIBRARY(dsse, m) {
   m.def("prefill_sample_commit(Tensor meta, Tensor new_ids, Tensor(a!) ids, Tensor(b!) ring, Tensor(c!) positions) -> ()");
   m.def("sample_penalties(Tensor(a!) logits, Tensor? active, Tensor pen_meta, Tensor hist, Tensor? row_slot=None, "
         "int vocab_offset=0, int vocab=2147483647) -> ()");
+  m.def("sample_bias_ban(Tensor(a!) logits, Tensor? active, Tensor ctl_meta, Tensor ctl_body, Tensor positions, "
+        "Tensor? row_slot=None, int vocab_offset=0, int vocab=2147483647) -> ()");
+  m.def("sample_candidates_min_p(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, "
+        "Tensor positions, Tensor? active, Tensor(a!) cand, Tensor ctl_meta, Tensor? row_slot=None, "
+        "int vocab_offset=0) -> ()");
   m.def("sample_pick_hist(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring, "
         "Tensor? ring_counter, Tensor(c!)? positions_inc, Tensor pen_meta, Tensor(d!) hist, "
         "int vocab=2147483647) -> ()");
@@ -1585,6 +1676,8 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("prefill_sample_gather", &prefill_sample_gather);
   m.impl("prefill_sample_commit", &prefill_sample_commit);
   m.impl("sample_penalties", &sample_penalties);
+  m.impl("sample_bias_ban", &sample_bias_ban);
+  m.impl("sample_candidates_min_p", &sample_candidates_min_p);
   m.impl("sample_pick_hist", &sample_pick_hist);
   m.impl("prefill_sample_commit_hist", &prefill_sample_commit_hist);
   m.impl("sample_hist_append", &sample_hist_append);

@@ -22,8 +22,18 @@ constexpr int kSThreads = 1024;   // filtered path: one workgroup per row
 constexpr int kSMaxV = 32768;     // per-rank vocab limit (row staged in 128 KiB of LDS)
 constexpr int kCThreads = 256;    // unfiltered path: one workgroup per (row, vocab chunk)
 
+// min_p of row b (0 = off): slot-indexed, through row_slot where the rows are not the slots.
+DEV float row_min_p(const SampleParams& p, int b) {
+  if (!p.min_p) return 0.f;
+  const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, p.ctl_slots, -1);
+  if ((unsigned)slot >= (unsigned)p.ctl_slots) return 0.f;
+  const float mp = p.min_p[slot];
+  return mp > 0.f ? fminf(mp, 1.f) : 0.f;
+}
+
 DEV bool row_filtered(const SampleParams& p, int b) {
-  return p.temperature[b] > 0.f && ((p.top_k[b] > 0 && p.top_k[b] < p.V) || p.top_p[b] < 1.f);
+  return p.temperature[b] > 0.f &&
+         ((p.top_k[b] > 0 && p.top_k[b] < p.V) || p.top_p[b] < 1.f || row_min_p(p, b) > 0.f);
 }
 
 // Score of one logit: greedy -> the logit itself; sampling -> logit/T + Gumbel(seed, pos, gidx).
@@ -141,6 +151,10 @@ __global__ void __launch_bounds__(kSThreads) sample_filtered_kernel(SampleParams
   const int tk = p.top_k[b];
   const float tp = p.top_p[b];
   if (tk > 0 && tk < p.V) thr = radix_select<false>(xs, p.V, xmax, 0u, (float)tk, hist);
+  // min_p: keep x_i / T - max_j x_j / T >= ln(min_p), one more top set of the same ordering -> one more key threshold
+  // (this rank's shard under TP, like top-k / top-p); the top-p mass select below then works on the survivors
+  const float mp = row_min_p(p, b);
+  if (mp > 0.f) thr = max(thr, fkey(xmax + log2f(mp)));
   if (tp < 1.f) {
     float z = 0.f;
     for (int i = threadIdx.x; i < p.V; i += kSThreads)
@@ -218,6 +232,41 @@ __global__ void __launch_bounds__(kSThreads) sample_penalty_kernel(float* __rest
     x -= freq * (float)c;
     if (c > 0u) x -= pres;
     row[i] = x;
+  }
+}
+
+// ---- logit_bias / min_tokens / stop_token_ids: the bias and ban pass ------------------------------------------
+// One workgroup per logits row, after the raw logprob statistics and before the penalties (vLLM's order).  The
+// slot's record (api.h: ctl_meta / ctl_body) is host-owned.  A row that is inactive, or whose slot has no bias entry
+// and no ban in force, returns at once (its logits stay bit-identical).  Otherwise x[id] += bias for every entry
+// (fp32; ids distinct), then, while the sampled token's position is below ban_until (generated tokens so far <
+// min_tokens; derived here because steps are enqueued ahead of the host), x[id] = -inf for every banned id.  Ids
+// outside this rank's vocab shard are skipped, so every TP rank runs the same launch.
+constexpr int kCtlThreads = 256;
+
+__global__ void __launch_bounds__(kCtlThreads) sample_bias_ban_kernel(float* __restrict__ logits, SampleParams p) {
+  const int b = blockIdx.x;
+  if (p.active && !p.active[b]) return;
+  const int Bm = p.ctl_slots;
+  const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, Bm, -1);
+  if ((unsigned)slot >= (unsigned)Bm) return;
+  const int nb = min(max(DSSE_IDX(p.ctl_meta[slot], kCtlBias + 1, 0), 0), kCtlBias);
+  int nban = min(max(DSSE_IDX(p.ctl_meta[Bm + slot], kCtlBan + 1, 0), 0), kCtlBan);
+  if (p.positions[b] + 1 >= p.ctl_meta[2 * Bm + slot]) nban = 0;  // min_tokens reached (or never set)
+  if (nb == 0 && nban == 0) return;
+  const int* body = p.ctl_body + (size_t)slot * kCtlBody;
+  float* row = logits + (size_t)b * p.ld;
+  for (int j = threadIdx.x; j < nb; j += kCtlThreads) {
+    const int v = DSSE_IDX(body[2 * j], p.v_global, -1) - p.vocab_offset;
+    if ((unsigned)v >= (unsigned)p.V) continue;  // another shard's token (or, checked build, a bad id)
+    row[v] += __int_as_float(body[2 * j + 1]);
+  }
+  if (nban == 0) return;  // (uniform over the workgroup)
+  __syncthreads();        // a banned id may also carry a bias: the ban is written last
+  for (int j = threadIdx.x; j < nban; j += kCtlThreads) {
+    const int v = DSSE_IDX(body[2 * kCtlBias + j], p.v_global, -1) - p.vocab_offset;
+    if ((unsigned)v >= (unsigned)p.V) continue;
+    row[v] = -INFINITY;
   }
 }
 
@@ -524,6 +573,17 @@ extern "C" hipError_t dsse_sample_penalties(int B, float* logits, const dsse::Sa
   return hipGetLastError();
 }
 
+// Bias and ban pass over logits [B, p->ld] in place (p: active, positions, V, ld, vocab_offset, v_global, ctl_meta,
+// ctl_body, ctl_slots, row_slot).
+extern "C" hipError_t dsse_sample_bias_ban(int B, float* logits, const dsse::SampleParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (p->V < 1 || p->ld < p->V || !logits || !p->ctl_meta || !p->ctl_body || !p->positions || p->ctl_slots < 1 ||
+      (!p->row_slot && B > p->ctl_slots))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::sample_bias_ban_kernel, dim3(B), dim3(dsse::kCtlThreads), 0, st, logits, *p);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t dsse_sample_hist_append(int n, const int* new_ids, const dsse::SampleParams* p,
                                               hipStream_t st) {
   if (n <= 0) return hipSuccess;
@@ -535,7 +595,7 @@ extern "C" hipError_t dsse_sample_hist_append(int n, const int* new_ids, const d
 // Per-rank candidate pass: fills p->cand[B, nchunks].
 extern "C" hipError_t dsse_sample(int B, const dsse::SampleParams* p, hipStream_t st) {
   if (B <= 0) return hipSuccess;
-  if (p->V > dsse::kSMaxV || p->nchunks < 1) return hipErrorInvalidValue;
+  if (p->V > dsse::kSMaxV || p->nchunks < 1 || (p->min_p && p->ctl_slots < 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dsse::sample_chunk_kernel, dim3(p->nchunks, B), dim3(dsse::kCThreads), 0, st, *p);
   hipLaunchKernelGGL(dsse::sample_filtered_kernel, dim3(B), dim3(dsse::kSThreads), 0, st, *p);
   return hipGetLastError();

@@ -35,6 +35,17 @@ std::string encode_request(const ChatRequest& r) {
   w.f64(r.frequency_penalty);
   w.f64(r.repetition_penalty);
   w.i32(r.logprobs);
+  w.i32(r.min_tokens);
+  w.f64(r.min_p);
+  w.i32((int32_t)r.logit_bias.size());
+  for (auto& kv : r.logit_bias) {
+    w.i32(kv.first);
+    w.f64(kv.second);
+  }
+  w.i32((int32_t)r.stop_token_ids.size());
+  for (int32_t t : r.stop_token_ids) w.i32(t);
+  w.i32((int32_t)r.stop.size());
+  for (auto& s : r.stop) w.str(s);
   return w.data();
 }
 
@@ -55,6 +66,20 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   r->frequency_penalty = rd.f64();
   r->repetition_penalty = rd.f64();
   r->logprobs = rd.i32();
+  r->min_tokens = rd.i32();
+  r->min_p = rd.f64();
+  int32_t n = rd.i32();
+  if (n < 0 || n > 300) return false;
+  for (int32_t i = 0; i < n && rd.good(); ++i) {
+    const int32_t t = rd.i32();
+    r->logit_bias.emplace_back(t, (float)rd.f64());
+  }
+  n = rd.i32();
+  if (n < 0 || n > 16) return false;
+  for (int32_t i = 0; i < n && rd.good(); ++i) r->stop_token_ids.push_back(rd.i32());
+  n = rd.i32();
+  if (n < 0 || n > 4) return false;
+  for (int32_t i = 0; i < n && rd.good(); ++i) r->stop.push_back(rd.str());
   return rd.good();
 }
 }  // namespace dpwire

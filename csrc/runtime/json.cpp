@@ -295,6 +295,25 @@ bool parse_json_array_of_objects(std::string_view text, std::vector<std::map<std
   }
 }
 
+bool parse_json_array_of_scalars(std::string_view text, std::vector<JsonValue>& out) {
+  Parser ps{text};
+  ps.ws();
+  if (ps.p >= text.size() || text[ps.p] != '[') return false;
+  ++ps.p;
+  ps.ws();
+  if (ps.p < text.size() && text[ps.p] == ']') return true;
+  while (true) {
+    JsonValue v;
+    if (!ps.value(v) || v.kind == JsonValue::kObject || v.kind == JsonValue::kArray) return false;
+    out.push_back(std::move(v));
+    ps.ws();
+    if (ps.p >= text.size()) return false;
+    if (text[ps.p] == ',') { ++ps.p; continue; }
+    if (text[ps.p] == ']') return true;
+    return false;
+  }
+}
+
 bool parse_json_object(std::string_view text, std::map<std::string, JsonValue>& out, size_t* consumed) {
   Parser ps{text};
   ps.ws();

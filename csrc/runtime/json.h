@@ -60,6 +60,10 @@ bool parse_json_object(std::string_view text, std::map<std::string, JsonValue>& 
 // malformed JSON or a non-object element.
 bool parse_json_array_of_objects(std::string_view text, std::vector<std::map<std::string, JsonValue>>& out);
 
+// Parse a JSON array of scalars (numbers, strings, bools, null), e.g. `stop` or `stop_token_ids`.  Returns false on
+// malformed JSON or a nested element.
+bool parse_json_array_of_scalars(std::string_view text, std::vector<JsonValue>& out);
+
 // Parse a TokenMessage (as published by the proxy / load generator).  Missing fields keep defaults.
 bool parse_token_message(std::string_view text, TokenMessage& m);
 

@@ -41,6 +41,13 @@ py::dict request_dict(const ChatRequest& r) {
   d["frequency_penalty"] = r.frequency_penalty;
   d["repetition_penalty"] = r.repetition_penalty;
   d["logprobs"] = r.logprobs;
+  py::list bias;
+  for (auto& kv : r.logit_bias) bias.append(py::make_tuple(kv.first, kv.second));
+  d["logit_bias"] = bias;  // [(token id, bias)]
+  d["min_tokens"] = r.min_tokens;
+  d["stop_token_ids"] = r.stop_token_ids;
+  d["min_p"] = r.min_p;
+  d["stop"] = r.stop;
   d["from_edge"] = r.from_edge;
   d["messages"] = r.messages_json;
   return d;
@@ -124,6 +131,7 @@ class Runtime {
 
   void set_vocab(std::vector<std::string> pieces) {
     if (dp_) dp_->set_vocab(pieces);
+    server_->set_vocab_size((int)pieces.size());
     vocab_ = std::move(pieces);
   }
 

@@ -248,10 +248,84 @@ bool parse_penalties(const std::map<std::string, JsonValue>& o, ChatRequest& r, 
          one("repetition_penalty", true, 0, &r.repetition_penalty);
 }
 
+// logit_bias, min_tokens, stop_token_ids, min_p and stop of a /chat or /v1/chat/completions body (vLLM's meaning;
+// limits 300 / 16 / 4).  Absent or JSON null = not given; anything else that is not exactly the expected shape and
+// range: false with *err naming the field -> 400.  `vocab` = the engine's vocabulary size (0: unknown, ids are
+// only checked to be non-negative int32); r.max_tokens must already be set (-1 = not given).
+bool parse_controls(const std::map<std::string, JsonValue>& o, ChatRequest& r, int vocab, std::string* err) {
+  auto field = [&](const char* k) -> const JsonValue* {
+    auto it = o.find(k);
+    return (it == o.end() || it->second.kind == JsonValue::kNull) ? nullptr : &it->second;
+  };
+  const double id_hi = vocab > 0 ? (double)vocab - 1 : 2147483647.0;
+  const std::string id_range = vocab > 0 ? "[0, " + std::to_string(vocab) + ")" : std::string("[0, 2^31)");
+  auto is_id = [&](double v) { return v >= 0 && v <= id_hi && v == std::floor(v); };
+  if (const JsonValue* v = field("logit_bias")) {
+    const std::string what = "logit_bias must be an object of at most 300 {\"token id in " + id_range +
+                             "\": bias in [-100, 100]} entries";
+    std::map<std::string, JsonValue> m;
+    if (v->kind != JsonValue::kObject || !parse_json_object(v->raw, m) || m.size() > 300) { *err = what; return false; }
+    std::map<int32_t, float> seen;
+    for (auto& kv : m) {
+      const std::string& k = kv.first;
+      if (k.empty() || k.size() > 10 || k.find_first_not_of("0123456789") != std::string::npos ||
+          !is_id(strtod(k.c_str(), nullptr)) || kv.second.kind != JsonValue::kNumber ||
+          !(kv.second.num >= -100 && kv.second.num <= 100)) {
+        *err = what;
+        return false;
+      }
+      seen[(int32_t)strtol(k.c_str(), nullptr, 10)] = (float)kv.second.num;  // ("7" and "007": the last one wins)
+    }
+    r.logit_bias.assign(seen.begin(), seen.end());
+  }
+  if (const JsonValue* v = field("stop_token_ids")) {
+    const std::string what = "stop_token_ids must be an array of at most 16 token ids in " + id_range;
+    std::vector<JsonValue> a;
+    if (v->kind != JsonValue::kArray || !parse_json_array_of_scalars(v->raw, a) || a.size() > 16) { *err = what; return false; }
+    for (auto& e : a) {
+      if (e.kind != JsonValue::kNumber || !is_id(e.num)) { *err = what; return false; }
+      r.stop_token_ids.push_back((int32_t)e.num);
+    }
+  }
+  if (const JsonValue* v = field("stop")) {
+    const std::string what = "stop must be a non-empty string or an array of at most 4 non-empty strings";
+    if (v->kind == JsonValue::kString) {
+      if (v->str.empty()) { *err = what; return false; }
+      r.stop.push_back(v->str);
+    } else {
+      std::vector<JsonValue> a;
+      if (v->kind != JsonValue::kArray || !parse_json_array_of_scalars(v->raw, a) || a.size() > 4) { *err = what; return false; }
+      for (auto& e : a) {
+        if (e.kind != JsonValue::kString || e.str.empty()) { *err = what; return false; }
+        r.stop.push_back(e.str);
+      }
+    }
+  }
+  if (const JsonValue* v = field("min_p")) {
+    if (v->kind != JsonValue::kNumber || !(v->num >= 0 && v->num <= 1)) {
+      *err = "min_p must be a number in [0, 1]";
+      return false;
+    }
+    r.min_p = v->num;
+  }
+  if (const JsonValue* v = field("min_tokens")) {
+    if (v->kind != JsonValue::kNumber || !(v->num >= 0 && v->num <= (1 << 20)) || v->num != std::floor(v->num)) {
+      *err = "min_tokens must be an integer in [0, max_tokens]";
+      return false;
+    }
+    if (r.max_tokens > 0 && v->num > r.max_tokens) {
+      *err = "min_tokens must not be greater than max_tokens";
+      return false;
+    }
+    r.min_tokens = (int)v->num;
+  }
+  return true;
+}
+
 // Optional sampling fields of a /chat body ({message, conversation_id} plus max_tokens, temperature, top_p,
 // top_k, seed, ignore_eos, and the three penalties above). Integers must be integral and in range BEFORE any conversion (a double outside the
 // target type's range is undefined behaviour to cast): false with *err otherwise -> 400.
-bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err) {
+bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err, int vocab) {
   auto num = [&](const char* k, double dflt) {
     auto it = o.find(k);
     return (it != o.end() && it->second.kind == JsonValue::kNumber) ? it->second.num : dflt;
@@ -284,7 +358,7 @@ bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, s
   r.top_p = top_p;
   auto ie = o.find("ignore_eos");
   r.ignore_eos = ie != o.end() && ie->second.kind == JsonValue::kBool && ie->second.b;
-  return true;
+  return parse_controls(o, r, vocab, err);
 }
 
 std::string http_error(int code, const std::string& msg, bool ka) {
@@ -844,6 +918,7 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   {
     std::string pen_err;
     if (!parse_penalties(o, r, &pen_err)) return bad(400, pen_err);
+    if (!parse_controls(o, r, srv_.vocab_size(), &pen_err)) return bad(400, pen_err);
   }
   {
     auto ie = o.find("ignore_eos");
@@ -1169,7 +1244,7 @@ void IoThread::handle_request(Conn& c, HttpRequest& req) {
       r.conversation_id = conv;
       r.message = msg;
       std::string perr;
-      if (!parse_sampling(o, r, &perr)) {
+      if (!parse_sampling(o, r, &perr, srv_.vocab_size())) {
         write_raw(c, http_error(400, perr, ka));
         return;
       }
@@ -1222,7 +1297,7 @@ void IoThread::handle_request(Conn& c, HttpRequest& req) {
     }
     ChatRequest sampling;
     std::string perr;
-    if (!parse_sampling(o, sampling, &perr)) {  // before any SSE byte: a bad parameter is a plain 400
+    if (!parse_sampling(o, sampling, &perr, srv_.vocab_size())) {  // before any SSE byte: a bad parameter is a plain 400
       write_raw(c, http_error(400, perr, ka));
       return;
     }

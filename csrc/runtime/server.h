@@ -89,6 +89,12 @@ struct ChatRequest {
   double frequency_penalty = 0;   // [-2, 2]
   double repetition_penalty = 1;  // (0, 2]
   int logprobs = -1;              // OpenAI route: -1 = off, 0..20 = top_logprobs of a request with logprobs: true
+  // vLLM's remaining sampling controls (both routes); the defaults mean "not given"
+  std::vector<std::pair<int32_t, float>> logit_bias;  // <= 300 (token id, bias in [-100, 100]), ids distinct
+  int min_tokens = 0;                                  // 0..max_tokens
+  std::vector<int32_t> stop_token_ids;                 // <= 16
+  double min_p = 0;                                    // [0, 1]
+  std::vector<std::string> stop;                       // <= 4 non-empty strings
   bool from_edge = false;   // submitted by the edge /chat (a subscriber exists)
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON
   // [{"role":..,"content":..},..]; empty = `message` is a single user turn
@@ -127,6 +133,9 @@ class Server {
   const ServerConfig& config() const { return cfg_; }
   void set_local_engine(bool on) { local_engine_.store(on); }
   void set_ready(bool on) { ready_.store(on); }
+  // Size of the engine's vocabulary (0 = unknown): token ids of a request are checked against it.
+  void set_vocab_size(int n) { vocab_size_.store(n); }
+  int vocab_size() const { return vocab_size_.load(); }
   // Conversations whose last subscriber left before completion (engine may abort them).
   std::vector<std::string> pop_cancellations();
   // Flow-control transitions since the last call: (conversation, paused).
@@ -167,6 +176,7 @@ class Server {
   std::atomic<bool> running_{false};
   std::atomic<bool> local_engine_{false};
   std::atomic<bool> ready_{true};
+  std::atomic<int> vocab_size_{0};
   std::atomic<uint64_t> next_req_{1};
   std::mutex cancel_mu_;
   std::vector<std::string> cancels_;

@@ -71,9 +71,25 @@ class SamplingParams:
     # raw logprobs (x - logsumexp(x) of the logits before penalties / temperature / filters) of every sampled token
     # and of the top N tokens: -1 = off, 0..20 = N (sampler.hip logprob_stats_kernel / logprob_finish_kernel)
     logprobs: int = -1
+    # vLLM's remaining controls.  logit_bias {token id: bias in [-100, 100]} (<= 300 entries) is added to the fp32
+    # logits after the raw logprob statistics and before the penalties, also under greedy; while fewer than
+    # min_tokens tokens are generated, EOS (unless ignore_eos) and every stop_token_ids entry get -inf
+    # (sampler.hip sample_bias_ban_kernel); a sampled stop_token_ids entry (<= 16) ends the stream as EOS does,
+    # ignore_eos or not; min_p in [0, 1] keeps, after temperature, the tokens with p_i >= min_p max_j p_j
+    # (sample_filtered_kernel).  `stop` strings are matched on the decoded text by the serving loop
+    # (serving/stop_strings.py): the engine itself only carries them.
+    logit_bias: dict | None = None
+    min_tokens: int = 0
+    stop_token_ids: tuple = ()
+    min_p: float = 0.0
+    stop: tuple = ()
 
     def penalised(self) -> bool:
         return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
+
+    def controlled(self) -> bool:
+        """Needs the device's bias and ban pass or min_p (stop_token_ids alone are the host's business)."""
+        return bool(self.logit_bias) or self.min_tokens > 0 or self.min_p > 0.0
 
 
 FINISH_CODES = {"": 0, "stop": 1, "length": 2, "abort": 3}  # runtime FinishReason (csrc/runtime/json.h)
@@ -328,6 +344,7 @@ class LLMEngine:
         self._dirty_slots: set = set()
         self._pen_live = False  # the device's penalty block holds a non-neutral slot (then _upload rewrites it)
         self._lp_live = False   # the device's lp_meta holds a slot that is on (likewise)
+        self._ctl_live = False  # the device's ctl_meta holds a non-neutral slot (likewise)
         self.ring_head = int(runner.ring_counter.item()) if runner.device.type == "cuda" else int(runner.ring_counter[0])
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0}
@@ -489,6 +506,21 @@ class LLMEngine:
             for i, s in live:
                 lpm[i] = min(int(s.params.logprobs), 20)
             self._lp_live = bool(live)
+        # ctl_meta [bias entries | banned ids | ban-until position | min_p]: likewise (the entries and ids themselves
+        # were uploaded at admission: ModelRunner.set_controls).  ban_until = orig_len + min_tokens does not change
+        # over a preemption and re-prefill.
+        ctl = None
+        live = [(i, s) for i, s in enumerate(self.slots) if s is not None and s.params.controlled()]
+        if live or self._ctl_live:
+            ctl = np.zeros(4 * Bm, dtype=np.int32)
+            for i, s in live:
+                p = s.params
+                bans = self._ban_ids(p)
+                ctl[i] = len(self._bias(p))
+                ctl[Bm + i] = len(bans)
+                ctl[2 * Bm + i] = s.orig_len + p.min_tokens if bans else 0
+                ctl[3 * Bm:].view(np.float32)[i] = min(max(float(p.min_p), 0.0), 1.0)
+            self._ctl_live = bool(live)
         bt_rows = {}
         for i in self._dirty_slots:
             s = self.slots[i]
@@ -509,6 +541,8 @@ class LLMEngine:
             put(r.pen_meta, torch.from_numpy(pen))
         if lpm is not None:
             put(r.lp_meta, torch.from_numpy(lpm))
+        if ctl is not None:
+            put(r.ctl_meta, torch.from_numpy(ctl))
         for i, row in bt_rows.items():
             put(r.block_tables[i], row)
         self._dirty_slots.clear()
@@ -530,6 +564,19 @@ class LLMEngine:
             packed = packed.pin_memory().to(r.device, non_blocking=True)
         n = len(idx)
         r.block_tables.view(-1).index_copy_(0, packed[:n].long(), packed[n:])
+
+    def _bias(self, p: SamplingParams) -> dict:
+        """logit_bias as {id: bias} over the ids the vocabulary has (ids distinct: the kernel's contract)."""
+        V = self.r.cfg.vocab_size
+        return {int(k): float(v) for k, v in (p.logit_bias or {}).items() if 0 <= int(k) < V}
+
+    def _ban_ids(self, p: SamplingParams) -> list:
+        """The ids min_tokens keeps from being sampled: EOS unless ignore_eos, then the stop_token_ids."""
+        if p.min_tokens <= 0:
+            return []
+        V = self.r.cfg.vocab_size
+        ids = ([] if p.ignore_eos else [int(self.eos_id)]) + [int(t) for t in p.stop_token_ids]
+        return [t for t in dict.fromkeys(ids) if 0 <= t < V]
 
     def _victim(self):
         """The sequence to preempt: paused ones first, then the most recent request (FCFS keeps the oldest)."""
@@ -581,7 +628,8 @@ class LLMEngine:
             if s.base == 0:  # first admission: clamp max_tokens to the context and to the whole pool
                 cap = self.alloc.num_blocks * PAGE - s.orig_len
                 max_new = max(1, min(s.params.max_tokens, r.max_model_len - s.orig_len, cap))
-                s.params = SamplingParams(**{**s.params.__dict__, "max_tokens": max_new})
+                s.params = SamplingParams(**{**s.params.__dict__, "max_tokens": max_new,
+                                             "min_tokens": max(0, min(int(s.params.min_tokens), max_new))})
             need = blocks_needed(len(s.prompt))
             idle = not any(x is not None for x in self.slots)
             if need > self.alloc.num_free - (0 if idle else self.watermark):
@@ -604,6 +652,10 @@ class LLMEngine:
                 r.set_history(s.slot, s.prompt, s.orig_len)
             if s.params.logprobs >= 0:
                 r.enable_logprobs()  # (the first such request captures the graph twins with the logprob passes)
+            if s.params.controlled():
+                # its bias entries and banned ids (again after a preemption: the slot may be another one); the first
+                # such request captures the graph twins with the bias and ban pass and min_p
+                r.set_controls(s.slot, self._bias(s.params), self._ban_ids(s.params))
 
     def _compact(self):
         """Move decoding sequences above the bucket their count needs into lower free / paused slots."""
@@ -883,7 +935,8 @@ class LLMEngine:
             elif self.on_itl and s.last_token_ns:
                 self.on_itl((now - s.last_token_ns) / 1e9)
             s.last_token_ns = now
-            is_eos = tok == self.eos_id and not s.params.ignore_eos
+            # a stop_token_ids entry ends the stream as EOS does (undelivered), whatever ignore_eos says
+            is_eos = (tok == self.eos_id and not s.params.ignore_eos) or tok in s.params.stop_token_ids
             if not is_eos:
                 ev = TokenEvent(s.conversation_id, tok, s.produced, False, timestamp_ns=now)
                 if s.params.logprobs >= 0 and lps is not None:

@@ -249,6 +249,14 @@ class ModelRunner:
         self.lp_ring = torch.zeros(RING_SIZE, Bm, ops.LP_OUT, device=dev, dtype=torch.float32)
         self.lp_used = False  # a request ever asked for logprobs (then the passes are launched / captured)
         self._lp_raw = None   # [rows, V] raw copy of the logprob rows, allocated once penalties AND logprobs are in use
+        # logit_bias / min_tokens / stop_token_ids / min_p (sampler.hip sample_bias_ban_kernel, row_min_p): ctl_meta =
+        # [bias entries | banned ids | ban-until position | min_p (float32 view)] per slot, host-owned and uploaded
+        # like slot_meta (all zero = neutral); ctl_body[slot] = [300 x (global id, bias bits) | 17 banned ids],
+        # written by the engine when a sequence that uses it takes the slot (set_controls)
+        self.ctl_meta = torch.zeros(4 * Bm, **i32)
+        self.min_p = self.ctl_meta[3 * Bm:].view(torch.float32)
+        self.ctl_body = torch.zeros(Bm, ops.CTL_BODY, **i32)
+        self.ctl_used = False  # a request ever used one of them (then the pass is launched / captured)
         # ---- decode activations ----
         bf = dict(device=dev, dtype=torch.bfloat16)
         self.resid = torch.zeros(Bm, H, device=dev, dtype=torch.float32)
@@ -289,8 +297,9 @@ class ModelRunner:
         self.pf_graphs = {}   # row bucket -> captured prefill graph
         self.pf = None        # static prefill buffers (allocated by capture)
         self.mx_graphs = {}   # decode bucket B -> [(chunk rows C, captured mixed prefill + decode graph)], C ascending
-        # their twins per (penalties used, logprobs used), each captured the first time that combination is needed
-        # (_capture_twins); pen_* = the (True, False) set: the penalty pass and nothing else new
+        # their twins per (penalties used, logprobs used[, True: the bias and ban pass / min_p used]), each captured
+        # the first time that combination is needed (_capture_twins); pen_* = the (True, False) set: the penalty pass
+        # and nothing else new
         self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs = {}, {}, {}
         self._twins = {(True, False): (self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs)}
         self._captured_key = (False, False)  # the passes the graphs of capture() hold (set there)
@@ -384,11 +393,14 @@ class ModelRunner:
         # logprob statistics before them: the penalty pass rewrites logits in place (same lazy launch / capture)
         if self.lp_used:
             raw = self._logprob_stats(self.logits[r], self.active[r], None, self._lp_bufs[B])
+        if self.ctl_used:  # (same lazy launch / capture) logit_bias and the min_tokens ban: after the raw statistics
+            ops.sample_bias_ban(self.logits[r], self.active[r], self.ctl_meta, self.ctl_body, self.positions[r], None,
+                                self.w.vocab_offset, self.cfg.vocab_size)
         if self.hist_used:
             ops.sample_penalties(self.logits[r], self.active[r], self.pen_meta, self.hist_state, None,
                                  self.w.vocab_offset, self.cfg.vocab_size)
-        ops.sample_candidates(self.logits[r], self.temperature[r], self.top_k[r], self.top_p[r], self.seeds[r],
-                              self.positions[r], self.active[r], cand, self.w.vocab_offset)
+        self._candidates(self.logits[r], self.temperature[r], self.top_k[r], self.top_p[r], self.seeds[r],
+                         self.positions[r], self.active[r], cand, None)
         if self.comm.size == 1:
             cand_all = cand.unsqueeze(0)
         else:
@@ -399,6 +411,15 @@ class ModelRunner:
         if self.lp_used:  # (before ring_advance: the same ring row the pick wrote)
             self._logprob_finish(self.logits[r], raw, self.ids[r], self.active[r], None, self._lp_bufs[B],
                                  ring_counter=self.ring_counter)
+
+    def _candidates(self, logits, temperature, top_k, top_p, seeds, positions, active, cand, row_slot) -> None:
+        """The candidate pass; with min_p (ctl_meta's fourth column, slot-indexed) once a request has used it."""
+        if self.ctl_used:
+            ops.sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions, active, cand,
+                                        self.ctl_meta, row_slot, self.w.vocab_offset)
+        else:
+            ops.sample_candidates(logits, temperature, top_k, top_p, seeds, positions, active, cand,
+                                  self.w.vocab_offset)
 
     # ------------------------------------------------------------------ logprobs
     def _lp_alloc(self, n: int) -> dict:
@@ -463,16 +484,44 @@ class ModelRunner:
             self.hist_used = True
             self._capture_twins()
 
+    def enable_controls(self) -> None:
+        """The first request with logit_bias, min_tokens, stop_token_ids or min_p: from now on every sampling site
+        runs the bias and ban pass (rows with nothing to do return at once) and the candidates read min_p; the graph
+        twins that hold them are replayed."""
+        if not self.ctl_used:
+            self.ctl_used = True
+            self._capture_twins()
+
+    def set_controls(self, slot: int, bias: dict, ban_ids: list) -> None:
+        """A sequence with logit_bias entries {global id: bias} and / or banned ids (min_tokens: EOS, stop_token_ids)
+        takes `slot`: they become the slot's ctl_body row, with one pinned non-blocking copy ordered after every step
+        already enqueued.  (The counts, ban_until and min_p travel in ctl_meta.)"""
+        if len(bias) > ops.CTL_BIAS or len(ban_ids) > ops.CTL_BAN:
+            raise ValueError(f"at most {ops.CTL_BIAS} logit_bias entries and {ops.CTL_BAN} banned ids per sequence")
+        row = np.zeros(ops.CTL_BODY, dtype=np.int32)
+        if bias:
+            row[0:2 * len(bias):2] = list(bias.keys())
+            row[1:2 * len(bias):2] = np.asarray(list(bias.values()), dtype=np.float32).view(np.int32)
+        row[2 * ops.CTL_BIAS:2 * ops.CTL_BIAS + len(ban_ids)] = ban_ids
+        row = torch.from_numpy(row)
+        if self.device.type == "cuda":
+            row = row.pin_memory()
+        self.ctl_body[slot].copy_(row, non_blocking=True)
+        self.enable_controls()
+
+    def _twin_key(self) -> tuple:
+        return (self.hist_used, self.lp_used) + ((True,) if self.ctl_used else ())
+
     def _capture_twins(self) -> None:
         """The first request that needs a new combination of (penalties, logprobs): every captured graph gets a twin
         with the penalty pass in front of the candidates and / or the logprob passes around them, replayed from now
         on; until then the graphs captured at startup run, which hold no such launch and no extra collective (an
         early-exit launch per step measured +8 us on the 4.23 ms 64-stream step: profiles/r7/penalties.md).  At most
-        three such captures in a process's life.  Stream capture executes nothing, so no decode state changes; the
+        three such captures in a process's life (seven with the bias and ban pass / min_p, the key's third flag).  Stream capture executes nothing, so no decode state changes; the
         shapes and buffers are the ones the startup capture warmed, and the logprob all-gathers run once eagerly
         first.  Deterministic across a TP group: every rank admits the same request in the same step."""
-        key = (self.hist_used, self.lp_used)
-        if key == (True, True) and self._lp_raw is None:
+        key = self._twin_key()
+        if key[:2] == (True, True) and self._lp_raw is None:
             self._lp_raw = torch.zeros(max(self.max_batch, PREFILL_GRAPH_SEQS), self.w.vocab_local,
                                        device=self.device, dtype=torch.float32)
         if key == self._captured_key or any(self._twins.get(key, ())) or \
@@ -504,13 +553,15 @@ class ModelRunner:
         torch.cuda.synchronize(self.device)
         self.twin_capture_s = time.perf_counter() - t0
         if self.comm.rank == 0:
-            what = " and ".join(n for n, on in zip(("the penalty pass", "the logprob passes"), key) if on)
+            what = " and ".join(n for n, on in zip(("the penalty pass", "the logprob passes",
+                                                    "the bias and ban pass / min_p"), key) if on)
             print(f"[engine] first request with this combination: captured the graphs with {what} "
                   f"({self.twin_capture_s:.2f} s)", flush=True)
 
     def _graph_set(self):
-        """(decode, prefill, mixed) graphs to replay: the twins that hold the passes in use (penalties, logprobs)."""
-        key = (self.hist_used, self.lp_used)
+        """(decode, prefill, mixed) graphs to replay: the twins that hold the passes in use (penalties, logprobs, the
+        bias and ban pass / min_p)."""
+        key = self._twin_key()
         if key == self._captured_key:
             return self.graphs, self.pf_graphs, self.mx_graphs
         return self._twins.get(key) or ({}, {}, {})
@@ -591,7 +642,7 @@ class ModelRunner:
         Neither: eager decode (reason logged)."""
         if not self.use_graphs:
             return
-        self._captured_key = (self.hist_used, self.lp_used)
+        self._captured_key = self._twin_key()
         for twins in self._twins.values():  # recorded against the previous capture's graphs and buffers
             for d in twins:
                 d.clear()
@@ -729,6 +780,10 @@ class ModelRunner:
         for t in (self.ids, self.positions) + ((self.hist_state,) if self.hist_used else ()) + \
                 ((self.lp_meta,) if self.lp_used else ()):
             t.index_copy_(0, di, t.index_select(0, si))
+        if self.ctl_used:  # the bias / ban records and their ctl_meta columns travel too
+            self.ctl_body.index_copy_(0, di, self.ctl_body.index_select(0, si))
+            m = self.ctl_meta.view(4, -1)
+            m.index_copy_(1, di, m.index_select(1, si))
 
     def decode(self, B: int) -> None:
         g = self._graph_set()[0].get(B)
@@ -930,15 +985,18 @@ class ModelRunner:
         sd = self.seeds.index_select(0, slot_idx).contiguous()
         nch = SAMPLE_CHUNKS if dev.type == "cuda" else 1
         cand = torch.zeros(nL, nch, 2, **f32)
-        slot_i32 = slot_idx.to(torch.int32) if self.hist_used or self.lp_used else None
+        slot_i32 = slot_idx.to(torch.int32) if self.hist_used or self.lp_used or self.ctl_used else None
         if self.lp_used:  # (eager passes: nothing is launched until a request has asked for logprobs / penalties)
             lp_bufs = self._lp_eager_bufs(nL)
             raw = self._logprob_stats(logits, None, slot_i32, lp_bufs)
+        if self.ctl_used:
+            ops.sample_bias_ban(logits, None, self.ctl_meta, self.ctl_body, last_pos, slot_i32, w.vocab_offset,
+                                cfg.vocab_size)
         if self.hist_used:
             # after a re-prefill the tokens already published count: the engine uploaded them with the history
             ops.sample_penalties(logits, None, self.pen_meta, self.hist_state, slot_i32, w.vocab_offset,
                                  cfg.vocab_size)
-        ops.sample_candidates(logits, temp, tk, tp, sd, last_pos, None, cand, w.vocab_offset)
+        self._candidates(logits, temp, tk, tp, sd, last_pos, None, cand, slot_i32)
         if comm.size == 1:
             cand_all = cand.unsqueeze(0)
         else:
@@ -1019,12 +1077,15 @@ class ModelRunner:
         active = sm[:ns]
         if self.lp_used:
             raw = self._logprob_stats(pf.s_logits, active, meta[ns:2 * ns], self._lp_pf)
-        if self.hist_used:  # gathered row i samples for slot meta[ns + i]: its penalties and history
+        if self.ctl_used:  # gathered row i samples for slot meta[ns + i]: its bias / ban record, penalties, history
+            ops.sample_bias_ban(pf.s_logits, active, self.ctl_meta, self.ctl_body, sm[6 * ns:7 * ns], meta[ns:2 * ns],
+                                w.vocab_offset, cfg.vocab_size)
+        if self.hist_used:
             ops.sample_penalties(pf.s_logits, active, self.pen_meta, self.hist_state, meta[ns:2 * ns],
                                  w.vocab_offset, cfg.vocab_size)
-        ops.sample_candidates(pf.s_logits, sm[ns:2 * ns].view(torch.float32), sm[2 * ns:3 * ns],
-                              sm[3 * ns:4 * ns].view(torch.float32), sm[4 * ns:6 * ns].view(ns, 2), sm[6 * ns:7 * ns],
-                              active, pf.s_cand, w.vocab_offset)
+        self._candidates(pf.s_logits, sm[ns:2 * ns].view(torch.float32), sm[2 * ns:3 * ns],
+                         sm[3 * ns:4 * ns].view(torch.float32), sm[4 * ns:6 * ns].view(ns, 2), sm[6 * ns:7 * ns],
+                         active, pf.s_cand, meta[ns:2 * ns])
         if comm.size == 1:
             cand_all = pf.s_cand.unsqueeze(0)
         else:

@@ -258,6 +258,36 @@ def sample_penalties(logits, active, pen_meta, hist, row_slot=None, vocab_offset
         ref.sample_penalties(logits, active, pen_meta, hist, row_slot, vocab_offset, vocab)
 
 
+CTL_BIAS, CTL_BAN, CTL_BODY = ref.CTL_BIAS, ref.CTL_BAN, ref.CTL_BODY  # logit_bias entries / banned ids / body words
+
+
+def sample_bias_ban(logits, active, ctl_meta, ctl_body, positions, row_slot=None, vocab_offset=0,
+                    vocab: int = 2**31 - 1):
+    """logit_bias and the min_tokens ban, in place on logits [B, V] (row stride >= V): after logprob_stats, before
+    sample_penalties.  ctl_meta int32 [4 Bm] = [bias entries | banned ids | ban-until position | min_p bits] per
+    slot; ctl_body int32 [Bm, 620] = [300 x (global id, bias float32 bits) | 17 banned ids | pad]; row b is slot
+    row_slot[b] (else b); positions[b] = the position of row b's predecessor token.  x[id] += bias, then x[id] = -inf
+    for the banned ids while positions[b] + 1 < ban_until.  Inactive rows and rows with nothing to do keep their
+    logits bit for bit."""
+    if _hip(logits):
+        torch.ops.dsse.sample_bias_ban(logits, active, ctl_meta, ctl_body, positions, row_slot, vocab_offset, vocab)
+    else:
+        ref.sample_bias_ban(logits, active, ctl_meta, ctl_body, positions, row_slot, vocab_offset, vocab)
+
+
+def sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions, active, cand, ctl_meta,
+                            row_slot=None, vocab_offset=0):
+    """sample_candidates with min_p (ctl_meta's fourth column, per slot; row b is slot row_slot[b], else b): after
+    temperature a sampling row keeps x_i / T - max_j x_j / T >= ln(min_p), then top-k and top-p act on the survivors.
+    0 = off; greedy rows are unaffected."""
+    if _hip(logits):
+        torch.ops.dsse.sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions, active, cand,
+                                               ctl_meta, row_slot, vocab_offset)
+    else:
+        ref.sample_candidates(logits, temperature, top_k, top_p, seeds, positions, active, cand, vocab_offset,
+                              ctl_meta, row_slot)
+
+
 def sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,
                      vocab: int = 2**31 - 1):
     """sample_pick whose picked token also joins hist[b] (device-side, stream-ordered) where slot b has penalties."""

@@ -232,9 +232,12 @@ def gumbel_noise(seed_lo: int, seed_hi: int, position: int, gidx: np.ndarray) ->
     return -np.log(-np.log(u))
 
 
-def _kept_mask(xb2: torch.Tensor, top_k: int, top_p: float) -> torch.Tensor:
-    """Elements kept by top-k then top-p (ties at the boundary kept), on base-2 scaled logits."""
+def _kept_mask(xb2: torch.Tensor, top_k: int, top_p: float, min_p: float = 0.0) -> torch.Tensor:
+    """Elements kept by min_p, top-k, then top-p (ties at the boundary kept), on base-2 scaled logits.  min_p keeps
+    x_i - max_j x_j >= log2(min_p); the three sets are top sets of one ordering, top-p's mass is the survivors'."""
     keep = torch.ones_like(xb2, dtype=torch.bool)
+    if min_p > 0.0:
+        keep &= xb2 >= xb2.max() + math.log2(min(min_p, 1.0))
     if 0 < top_k < xb2.numel():
         kth = torch.topk(xb2, top_k).values[-1]
         keep &= xb2 >= kth
@@ -251,14 +254,14 @@ def _kept_mask(xb2: torch.Tensor, top_k: int, top_p: float) -> torch.Tensor:
 
 
 def sample_row(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seed: tuple, position: int,
-               vocab_offset: int = 0):
+               vocab_offset: int = 0, min_p: float = 0.0):
     """Returns (score, global index) exactly as the HIP sampler computes them."""
     x = logits.double()
     if not temperature > 0:
         i = int(torch.argmax(x))
         return float(x[i]), i + vocab_offset
     xb2 = (x / temperature) * (1.0 / math.log(2.0))
-    keep = _kept_mask(xb2, top_k, top_p)
+    keep = _kept_mask(xb2, top_k, top_p, min_p)
     gidx = np.arange(x.numel(), dtype=np.uint64) + np.uint64(vocab_offset)
     g = torch.from_numpy(gumbel_noise(seed[0], seed[1], position, gidx))
     sc = torch.where(keep, xb2 * math.log(2.0) + g, torch.full_like(xb2, float("-inf")))
@@ -266,9 +269,12 @@ def sample_row(logits: torch.Tensor, temperature: float, top_k: int, top_p: floa
     return float(sc[i]), i + vocab_offset
 
 
-def sample_candidates(logits, temperature, top_k, top_p, seeds, positions, active, cand, vocab_offset=0):
-    """cand [B, C, 2]: the whole-row best goes to chunk 0, other chunks get -inf (same final pick)."""
+def sample_candidates(logits, temperature, top_k, top_p, seeds, positions, active, cand, vocab_offset=0,
+                      ctl_meta=None, row_slot=None):
+    """cand [B, C, 2]: the whole-row best goes to chunk 0, other chunks get -inf (same final pick).  With ctl_meta
+    (sample_candidates_min_p): min_p of row b = ctl_meta's fourth column at slot row_slot[b] (else b)."""
     B = logits.shape[0]
+    min_p = ctl_meta.view(-1)[3 * (ctl_meta.numel() // 4):].view(torch.float32) if ctl_meta is not None else None
     sd = seeds.reshape(-1).tolist()
     cand[..., 0] = float("-inf")
     cand[..., 1] = 0.0
@@ -276,8 +282,9 @@ def sample_candidates(logits, temperature, top_k, top_p, seeds, positions, activ
         if active is not None and not int(active[b]):
             continue
         seed = (sd[2 * b] & _U32, sd[2 * b + 1] & _U32)
+        mp = float(min_p[int(row_slot[b]) if row_slot is not None else b]) if min_p is not None else 0.0
         sc, idx = sample_row(logits[b], float(temperature[b]), int(top_k[b]), float(top_p[b]), seed,
-                             int(positions[b]), vocab_offset)
+                             int(positions[b]), vocab_offset, mp)
         cand[b, 0, 0] = sc
         cand[b, 0, 1] = float(idx)  # CPU encoding: the index as a float value (GPU: its bit pattern)
 
@@ -385,6 +392,42 @@ def sample_penalties(logits, active, pen_meta, hist, row_slot=None, vocab_offset
             if c > 0:
                 x = x - p
             logits[b, v] = x
+
+
+# ---- logit_bias / min_tokens / stop_token_ids (sampler.hip sample_bias_ban_kernel) ----
+# ctl_meta int32 [4 Bm] = [bias entries | banned ids | ban-until position | min_p (float32 bits)] per slot; ctl_body
+# int32 [Bm, CTL_BODY]: CTL_BIAS x (global id, bias float32 bits), then CTL_BAN banned global ids.
+CTL_BIAS, CTL_BAN = 300, 17
+CTL_BODY = 2 * CTL_BIAS + CTL_BAN + 3
+
+
+def sample_bias_ban(logits, active, ctl_meta, ctl_body, positions, row_slot=None, vocab_offset=0,
+                    vocab: int = 2**31 - 1):
+    """In place on logits [B, V] (row b = slot row_slot[b], else b), in fp32: x[id] += bias for the slot's entries,
+    then, while positions[b] + 1 < ban_until, x[id] = -inf for its banned ids.  Inactive rows and rows whose slot
+    has no entry and no ban in force are not touched; ids outside [vocab_offset, vocab_offset + V) are skipped."""
+    B, V = logits.shape
+    Bm = ctl_meta.numel() // 4
+    for b in range(B):
+        if active is not None and not int(active[b]):
+            continue
+        slot = int(row_slot[b]) if row_slot is not None else b
+        nb = min(max(int(ctl_meta[slot]), 0), CTL_BIAS)
+        nban = min(max(int(ctl_meta[Bm + slot]), 0), CTL_BAN)
+        if int(positions[b]) + 1 >= int(ctl_meta[2 * Bm + slot]):
+            nban = 0
+        if nb == 0 and nban == 0:
+            continue
+        ids = ctl_body[slot, 0:2 * nb:2].tolist()
+        bias = ctl_body[slot, 1:2 * nb:2].contiguous().view(torch.float32)
+        for j, t in enumerate(ids):
+            v = t - vocab_offset
+            if 0 <= v < V and 0 <= t < vocab:
+                logits[b, v] = logits[b, v] + bias[j]
+        for t in ctl_body[slot, 2 * CTL_BIAS:2 * CTL_BIAS + nban].tolist():
+            v = t - vocab_offset
+            if 0 <= v < V and 0 <= t < vocab:
+                logits[b, v] = float("-inf")
 
 
 def _hist_append(pen_meta, hist, slot: int, tok: int) -> None:

@@ -28,6 +28,7 @@ from ..models.mistral import TINY, get_config, init_standard_weights
 from ..models.tokenizer import get_tokenizer, prompt_for_request
 from .config import ServeConfig
 from .faults import FaultPlan, StepTracer, Watchdog
+from .stop_strings import StopMatcher
 
 
 def build_engine(cfg: ServeConfig, device=None, comm=None):
@@ -72,6 +73,7 @@ class EngineLoop(threading.Thread):
 
     halted = False
     pub_lock = threading.Lock()  # class default (a loop built without __init__); each loop sets its own
+    stops = None                 # (likewise: no stop-string matching)
 
     def __init__(self, runtime, engine: LLMEngine, tokenizer, cfg: ServeConfig):
         super().__init__(daemon=True, name="engine-loop")
@@ -92,6 +94,8 @@ class EngineLoop(threading.Thread):
         self.last_progress = time.monotonic()
         self.steps = 0
         self.tokenize_errors = 0
+        # stop strings are matched where the text exists: on the events this loop publishes (serving/stop_strings.py)
+        self.stops = StopMatcher(tokenizer.piece)
         # just-in-time enqueue (LLMEngine.jit_delay): the host work that must fit between polling the requests and
         # the in-flight step's end; DSSE_JIT_MARGIN_MS=0 enqueues every step at once (one queued ahead)
         self.jit_margin_s = float(os.environ.get("DSSE_JIT_MARGIN_MS", "1.5")) / 1e3
@@ -117,7 +121,24 @@ class EngineLoop(threading.Thread):
             frequency_penalty=float(req.get("frequency_penalty", d.frequency_penalty)),
             repetition_penalty=float(req.get("repetition_penalty", d.repetition_penalty)),
             # -1 = off, else top_logprobs (0..20) of an OpenAI request with logprobs: true
-            logprobs=int(req.get("logprobs", -1)))
+            logprobs=int(req.get("logprobs", -1)),
+            # (validated by the HTTP server: <= 300 (id, bias) pairs, <= 16 ids, <= 4 strings)
+            logit_bias={int(t): float(b) for t, b in req.get("logit_bias") or ()} or None,
+            min_tokens=int(req.get("min_tokens", 0)), stop_token_ids=tuple(int(t) for t in req.get("stop_token_ids") or ()),
+            min_p=float(req.get("min_p", 0.0)), stop=tuple(req.get("stop") or ()))
+
+    def _watch_stop(self, req, prompt, params: SamplingParams) -> None:
+        """A request with stop strings: its events pass through the matcher from now on."""
+        if self.stops is not None and params is not None and params.stop:
+            n = min(len(prompt), self.engine.r.max_model_len - 1)  # (what the engine keeps of the prompt)
+            self.stops.register(req["conversation_id"], params.stop, min(params.min_tokens, params.max_tokens), n)
+
+    def stop_aborts(self) -> list:
+        """Conversations a stop string ended since the last call: the loop aborts them in the engine."""
+        if self.stops is None:
+            return []
+        with self.pub_lock:
+            return self.stops.pop_aborts()
 
     def flow_events(self) -> list:
         """Flow-control transitions from the runtime plus pauses that outlived ``max_pause_s``."""
@@ -137,7 +158,10 @@ class EngineLoop(threading.Thread):
         with self.pub_lock:
             if self.halted and not final:
                 return
-            self._publish(events)
+            if self.stops is not None:
+                events = self.stops.filter(events)
+            if events:
+                self._publish(events)
 
     def _lp_item(self, token_id: int, logprob: float) -> str:
         """{"token": piece, "logprob": f, "bytes": [the piece's UTF-8 bytes]} without the closing brace.  %.9g
@@ -180,7 +204,9 @@ class EngineLoop(threading.Thread):
         for req in reqs:
             prompt = self.tokenize(req)
             if prompt is not None:
-                self.engine.add_request(req["conversation_id"], prompt, self._params(req), arrival_ns=req["arrival_ns"])
+                params = self._params(req)
+                self._watch_stop(req, prompt, params)
+                self.engine.add_request(req["conversation_id"], prompt, params, arrival_ns=req["arrival_ns"])
 
     def _jit_wait(self):
         """Wait until the just-in-time deadline (LLMEngine.jit_delay), taking in the requests that arrive meanwhile
@@ -235,7 +261,7 @@ class EngineLoop(threading.Thread):
                 # only paused streams left: wait briefly so their resume events get through
                 wait = 0 if busy else (2 if self.engine.has_work() else 20)
                 self._take(self.rt.poll_requests(256, wait))
-                for conv in self.rt.pop_cancellations():
+                for conv in list(self.rt.pop_cancellations()) + self.stop_aborts():
                     self.engine.abort(conv)
                 for conv, paused in self.flow_events():
                     self.engine.set_paused(conv, paused)

@@ -50,8 +50,10 @@ class TPLeaderLoop(EngineLoop):
                 for req in self.rt.poll_requests(256, wait):
                     prompt = self.tokenize(req)
                     if prompt is not None:
-                        self.drv.add(req["conversation_id"], prompt, self._params(req), req["arrival_ns"])
-                for conv in self.rt.pop_cancellations():
+                        params = self._params(req)
+                        self._watch_stop(req, prompt, params)  # (stop strings stay here: only the leader has text)
+                        self.drv.add(req["conversation_id"], prompt, params, req["arrival_ns"])
+                for conv in list(self.rt.pop_cancellations()) + self.stop_aborts():
                     self.drv.abort(conv)
                 for conv, paused in self.flow_events():  # pause timeouts are decided here, so all ranks agree
                     self.drv.set_paused(conv, paused)

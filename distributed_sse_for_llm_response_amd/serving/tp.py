@@ -69,8 +69,14 @@ class Plan:
                 s_lo, s_hi = sd & 0x7FFFFFFF, (sd >> 31) & 0x7FFFFFFF
             w += [rid, arrival & 0x7FFFFFFF, (arrival >> 31) & 0x7FFFFFFF, int(p.max_tokens), int(p.top_k), s_lo, s_hi,
                   int(bool(p.ignore_eos)), _f2i(p.temperature), _f2i(p.top_p), _f2i(p.presence_penalty),
-                  _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), int(p.logprobs), len(prompt)]
+                  _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), int(p.logprobs), int(p.min_tokens),
+                  _f2i(p.min_p), len(p.logit_bias or ()), len(p.stop_token_ids), len(prompt)]
             w += [int(t) for t in prompt]
+            # variable-length like the prompt: the logit_bias (id, bias bits) pairs, then the stop_token_ids (stop
+            # strings stay with the leader: only it has text)
+            for t, b in (p.logit_bias or {}).items():
+                w += [int(t), _f2i(b)]
+            w += [int(t) for t in p.stop_token_ids]
         for rid in self.aborts:
             w.append(rid)
         for rid, paused in self.flow:
@@ -82,14 +88,19 @@ class Plan:
         p = Plan(step=bool(flags & F_STEP), stop=bool(flags & F_STOP), sync=bool(flags & F_SYNC))
         o = 0
         for _ in range(n_add):
-            rid, a_lo, a_hi, mt, tk, s_lo, s_hi, ie, temp, top_p, pres, freq, rep, lp, n = w[o:o + 15]
-            o += 15
+            rid, a_lo, a_hi, mt, tk, s_lo, s_hi, ie, temp, top_p, pres, freq, rep, lp, mn, min_p, nb, ns, n = w[o:o + 19]
+            o += 19
             prompt = w[o:o + n]
             o += n
+            bias = {w[o + 2 * j]: _i2f(w[o + 2 * j + 1]) for j in range(nb)}
+            o += 2 * nb
+            stop_ids = tuple(w[o:o + ns])
+            o += ns
             sp = SamplingParams(temperature=_i2f(temp), top_p=_i2f(top_p), top_k=tk, max_tokens=mt,
                                 seed=None if s_lo < 0 else s_lo | (s_hi << 31), ignore_eos=bool(ie),
                                 presence_penalty=_i2f(pres), frequency_penalty=_i2f(freq),
-                                repetition_penalty=_i2f(rep), logprobs=lp)
+                                repetition_penalty=_i2f(rep), logprobs=lp, logit_bias=bias or None, min_tokens=mn,
+                                stop_token_ids=stop_ids, min_p=_i2f(min_p))
             p.adds.append((rid, prompt, sp, a_lo | (a_hi << 31)))
         for _ in range(n_abort):
             p.aborts.append(w[o])
