@@ -152,6 +152,42 @@ struct LogprobParams {
   int ring_row;
 };
 
+// Guided decoding (sampler.hip guide_live_kernel / sample_guide_mask_kernel / sample_guide_advance_kernel): a byte-level
+// DFA per pattern, walked on the device so that no step waits for the host to look at a token.
+//   tok_bytes [v_global, kGuideTokBytes] / tok_len [v_global] (uint8): the UTF-8 bytes of every piece of the global
+//     vocabulary, whole on every TP rank, built once from the tokenizer.  Length 0 = never allowed under a guide
+//     (<unk>, <s>, </s>, empty pieces, pieces longer than kGuideTokBytes).
+//   guide_tab [kGuidePool, kGuideStates, 256] (uint16): the transition tables of the resident patterns, start state 0,
+//     kGuideDead = dead; every entry is a state below kGuideStates or kGuideDead (the kernels treat anything else as
+//     dead).  guide_flags [kGuidePool, kGuideStates] (int32): bit 0 = accepting (host, with the table), bit 1 = stuck
+//     = no token of the global vocabulary other than EOS survives from the state (guide_live_kernel, once per upload).
+//   guide_meta [2, slots] (int32): word [slot] = pool index of the slot's pattern, -1 = guide off (the neutral value);
+//     word [slots + slot] = the current DFA state, kGuideDead = dead.  The host writes both words when a sequence takes
+//     the slot (state = the walk over the tokens already published), stream-ordered; from then on only the advance
+//     kernel writes the state.  Pool entries are host-owned and reference-counted by live sequences.
+constexpr int kGuideStates = 512;
+constexpr int kGuidePool = 32;     // resident patterns (32 x 512 x 256 x 2 B = 8 MiB)
+constexpr int kGuideTokBytes = 32;
+constexpr int kGuideDead = 0xFFFF;
+struct GuideParams {
+  const unsigned char* tok_bytes;
+  const unsigned char* tok_len;
+  const unsigned short* tab;
+  int* flags;
+  int* meta;               // [2, slots]
+  int slots, pool;
+  int v_global, eos;       // EOS's global id (< 0: none)
+  const int* active;       // [B] or null
+  const int* row_slot;     // [B] slot of row b, or null (row b = slot b)
+  // mask pass
+  float* logits;           // [B, ld], this rank's shard
+  int ld, V, vocab_offset;
+  // advance pass
+  const int* ids;          // [B] committed (global) ids
+  // live pass
+  int entry, n_states;     // the pool entry just uploaded and its used states
+};
+
 }  // namespace dsse
 
 extern "C" {
@@ -180,6 +216,9 @@ hipError_t dsse_prefill_sample_commit(const int* meta, int NS, const int* new_id
                                       int* positions, const int* pen_meta, int* hist, int hist_ld, hipStream_t st);
 hipError_t dsse_sample_penalties(int B, float* logits, const dsse::SampleParams* p, hipStream_t st);
 hipError_t dsse_sample_bias_ban(int B, float* logits, const dsse::SampleParams* p, hipStream_t st);
+hipError_t dsse_guide_live(const dsse::GuideParams* p, hipStream_t st);
+hipError_t dsse_sample_guide_mask(int B, const dsse::GuideParams* p, hipStream_t st);
+hipError_t dsse_sample_guide_advance(int B, const dsse::GuideParams* p, hipStream_t st);
 hipError_t dsse_sample_hist_append(int n, const int* new_ids, const dsse::SampleParams* p, hipStream_t st);
 hipError_t dsse_logprob_stats(int B, const dsse::LogprobParams* p, hipStream_t st);
 hipError_t dsse_logprob_chosen(int B, const dsse::LogprobParams* p, hipStream_t st);

@@ -1190,6 +1190,107 @@ void sample_candidates_min_p(const Tensor& logits, const Tensor& temperature, co
   DSSE_CHECK_HIP(dsse_sample(B, &p, cur_stream()));
 }
 
+// ---- guided decoding (sampler.hip guide_live / sample_guide_mask / sample_guide_advance; records: api.h) ---------
+// tok_bytes uint8 [V_global, 32], tok_len uint8 [V_global], guide_tab int16 (uint16 bits) [pool, 512, 256],
+// guide_flags int32 [pool, 512], guide_meta int32 [2 x slots].
+dsse::GuideParams guide_params(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& guide_tab,
+                               const Tensor& guide_flags, const Tensor& guide_meta, int64_t eos) {
+  check_gpu(tok_bytes, "tok_bytes");
+  check_dtype(tok_bytes, at::kByte, "tok_bytes");
+  check_gpu(tok_len, "tok_len");
+  check_dtype(tok_len, at::kByte, "tok_len");
+  check_gpu(guide_tab, "guide_tab");
+  check_dtype(guide_tab, at::kShort, "guide_tab");
+  check_gpu(guide_flags, "guide_flags");
+  check_dtype(guide_flags, at::kInt, "guide_flags");
+  check_gpu(guide_meta, "guide_meta");
+  check_dtype(guide_meta, at::kInt, "guide_meta");
+  TORCH_CHECK(tok_bytes.dim() == 2 && tok_bytes.is_contiguous() && tok_bytes.size(1) == dsse::kGuideTokBytes &&
+                  tok_bytes.size(0) >= 1 && tok_bytes.size(0) <= INT32_MAX, "tok_bytes must be a contiguous [V, 32]");
+  TORCH_CHECK(tok_len.is_contiguous() && tok_len.numel() == tok_bytes.size(0), "tok_len must be [V]");
+  TORCH_CHECK(guide_tab.dim() == 3 && guide_tab.is_contiguous() && guide_tab.size(0) >= 1 &&
+                  guide_tab.size(0) <= dsse::kGuidePool && guide_tab.size(1) == dsse::kGuideStates &&
+                  guide_tab.size(2) == 256, "guide_tab must be a contiguous [pool <= 32, 512, 256]");
+  TORCH_CHECK(guide_flags.dim() == 2 && guide_flags.is_contiguous() && guide_flags.size(0) == guide_tab.size(0) &&
+                  guide_flags.size(1) == dsse::kGuideStates, "guide_flags must be a contiguous [pool, 512]");
+  TORCH_CHECK(guide_meta.is_contiguous() && guide_meta.numel() >= 2 && guide_meta.numel() % 2 == 0 &&
+                  guide_meta.numel() / 2 <= INT32_MAX, "guide_meta must be [2 x slots]");
+  dsse::GuideParams p{};
+  p.tok_bytes = tok_bytes.data_ptr<uint8_t>();
+  p.tok_len = tok_len.data_ptr<uint8_t>();
+  p.tab = reinterpret_cast<const unsigned short*>(guide_tab.data_ptr<int16_t>());
+  p.flags = guide_flags.data_ptr<int>();
+  p.meta = guide_meta.data_ptr<int>();
+  p.slots = (int)(guide_meta.numel() / 2);
+  p.pool = (int)guide_tab.size(0);
+  p.v_global = (int)tok_bytes.size(0);
+  p.eos = (int)std::max<int64_t>(std::min<int64_t>(eos, INT32_MAX), -1);
+  return p;
+}
+
+void guide_rows(dsse::GuideParams& p, const c10::optional<Tensor>& active, const c10::optional<Tensor>& row_slot,
+                int B) {
+  if (active.has_value()) {
+    check_gpu(*active, "active");
+    check_dtype(*active, at::kInt, "active");
+    TORCH_CHECK(active->is_contiguous() && active->numel() >= B, "active too short");
+    p.active = active->data_ptr<int>();
+  }
+  if (row_slot.has_value()) {
+    check_gpu(*row_slot, "row_slot");
+    check_dtype(*row_slot, at::kInt, "row_slot");
+    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
+    p.row_slot = row_slot->data_ptr<int>();
+  } else {
+    TORCH_CHECK(B <= p.slots, "more rows than slots (no row_slot map)");
+  }
+}
+
+// Once per table upload, on the stream, before first use: the stuck bits of pool entry `entry`'s first n_states states.
+void guide_live(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& guide_tab, Tensor& guide_flags,
+                const Tensor& guide_meta, int64_t entry, int64_t n_states, int64_t eos) {
+  dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
+  TORCH_CHECK(entry >= 0 && entry < p.pool && n_states >= 1 && n_states <= dsse::kGuideStates, "bad entry / n_states");
+  p.entry = (int)entry;
+  p.n_states = (int)n_states;
+  DSSE_CHECK_HIP(dsse_guide_live(&p, cur_stream()));
+}
+
+// In place on logits [B, V] (row stride >= V): after the penalties, immediately before the candidates.
+void sample_guide_mask(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& tok_bytes,
+                       const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
+                       const Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t vocab_offset,
+                       int64_t eos) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");
+  check_dtype(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
+                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
+  const int B = (int)logits.size(0), V = (int)logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= 32768, "sampler supports V <= 32768 per rank");
+  dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
+  TORCH_CHECK(vocab_offset >= 0 && vocab_offset <= INT32_MAX - 32768, "bad vocab_offset");
+  guide_rows(p, active, row_slot, B);
+  p.logits = logits.data_ptr<float>();
+  p.ld = (int)logits.stride(0);
+  p.V = V;
+  p.vocab_offset = (int)vocab_offset;
+  DSSE_CHECK_HIP(dsse_sample_guide_mask(B, &p, cur_stream()));
+}
+
+// After a commit: the guide state of row b's slot advances by ids[b] (global ids).
+void sample_guide_advance(const Tensor& ids, const c10::optional<Tensor>& active, const Tensor& tok_bytes,
+                          const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
+                          Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t eos) {
+  check_gpu(ids, "ids");
+  check_dtype(ids, at::kInt, "ids");
+  TORCH_CHECK(ids.is_contiguous() && ids.numel() <= INT32_MAX, "ids must be contiguous");
+  const int B = (int)ids.numel();
+  dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
+  guide_rows(p, active, row_slot, B);
+  p.ids = ids.data_ptr<int>();
+  DSSE_CHECK_HIP(dsse_sample_guide_advance(B, &p, cur_stream()));
+}
+
 // sample_pick whose picked token also joins hist[b] where slot b has penalties on.
 void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
                       const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
@@ -1625,6 +1726,12 @@ TORCH_LIBRARY(dsse, m) {
   m.def("sample_candidates_min_p(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, "
         "Tensor positions, Tensor? active, Tensor(a!) cand, Tensor ctl_meta, Tensor? row_slot=None, "
         "int vocab_offset=0) -> ()");
+  m.def("guide_live(Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, Tensor(a!) guide_flags, Tensor guide_meta, "
+        "int entry, int n_states, int eos) -> ()");
+  m.def("sample_guide_mask(Tensor(a!) logits, Tensor? active, Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, "
+        "Tensor guide_flags, Tensor guide_meta, Tensor? row_slot=None, int vocab_offset=0, int eos=-1) -> ()");
+  m.def("sample_guide_advance(Tensor ids, Tensor? active, Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, "
+        "Tensor guide_flags, Tensor(a!) guide_meta, Tensor? row_slot=None, int eos=-1) -> ()");
   m.def("sample_pick_hist(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring, "
         "Tensor? ring_counter, Tensor(c!)? positions_inc, Tensor pen_meta, Tensor(d!) hist, "
         "int vocab=2147483647) -> ()");
@@ -1678,6 +1785,9 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("sample_penalties", &sample_penalties);
   m.impl("sample_bias_ban", &sample_bias_ban);
   m.impl("sample_candidates_min_p", &sample_candidates_min_p);
+  m.impl("guide_live", &guide_live);
+  m.impl("sample_guide_mask", &sample_guide_mask);
+  m.impl("sample_guide_advance", &sample_guide_advance);
   m.impl("sample_pick_hist", &sample_pick_hist);
   m.impl("prefill_sample_commit_hist", &prefill_sample_commit_hist);
   m.impl("sample_hist_append", &sample_hist_append);

@@ -270,6 +270,96 @@ __global__ void __launch_bounds__(kCtlThreads) sample_bias_ban_kernel(float* __r
   }
 }
 
+// ---- guided decoding: DFA token masking (api.h GuideParams) ------------------------------------------------------
+// The walk of one token's bytes from `state`: the state reached, kGuideDead where a byte has no transition.  Length 0
+// (or above kGuideTokBytes) = a token no guide allows.  Table entries are read through the vector L1 / L2: a used
+// table is at most 256 KiB and the rows of the few states a step visits stay resident (profiles/r10/guided_decoding.md).
+DEV int guide_walk(const GuideParams& p, const unsigned short* __restrict__ tab, int state, int g) {
+  const int len = p.tok_len[g];
+  if (len < 1 || len > kGuideTokBytes) return kGuideDead;
+  const uint4* src = reinterpret_cast<const uint4*>(p.tok_bytes + (size_t)g * kGuideTokBytes);
+  const uint4 lo = src[0], hi = src[1];
+  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+  for (int j = 0; j < kGuideTokBytes; ++j) {  // (unrolled: w[] stays in registers)
+    if (j >= len) break;
+    const int byte = (w[j >> 2] >> (8 * (j & 3))) & 0xff;
+    state = tab[(size_t)state * 256 + byte];
+    if (state >= kGuideStates) return kGuideDead;  // dead (or, never written by the host, an entry out of range)
+  }
+  return state;
+}
+
+// The guide of row b: false = nothing to do (inactive row, guide off, dead state).
+DEV bool guide_row(const GuideParams& p, int b, int* slot_out, int* entry_out, int* state_out) {
+  if (p.active && !p.active[b]) return false;
+  const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, p.slots, -1);
+  if ((unsigned)slot >= (unsigned)p.slots) return false;
+  const int entry = DSSE_IDX(p.meta[slot], p.pool, -1);
+  if ((unsigned)entry >= (unsigned)p.pool) return false;
+  *slot_out = slot;
+  *entry_out = entry;
+  *state_out = p.meta[p.slots + slot];
+  return true;
+}
+
+constexpr int kGuideThreads = 1024;
+
+// Once per table upload, one workgroup per used state: bit 1 of its flag = no token of the global vocabulary other
+// than EOS survives from it (the same on every TP rank: the table walked is the global one).
+__global__ void __launch_bounds__(kGuideThreads) guide_live_kernel(GuideParams p) {
+  const int s = blockIdx.x;
+  const unsigned short* tab = p.tab + (size_t)p.entry * kGuideStates * 256;
+  int any = 0;
+  for (int g = threadIdx.x; g < p.v_global && !any; g += kGuideThreads)
+    if (g != p.eos && guide_walk(p, tab, s, g) != kGuideDead) any = 1;
+  any = __syncthreads_or(any);
+  if (threadIdx.x == 0) {
+    int* f = p.flags + (size_t)p.entry * kGuideStates + s;
+    *f = (*f & 1) | (any ? 0 : 2);
+  }
+}
+
+// One workgroup per logits row, after the penalties and immediately before the candidate pass.  An inactive row, a
+// slot with the guide off and a slot whose state is dead (steps enqueued past the stream's end) return at once, the
+// row bit-identical.  Otherwise column v (global id g = v + vocab_offset) keeps its bits iff g is allowed: EOS iff the
+// state is accepting or stuck, any other token iff its bytes walk from the state without meeting dead; the rest
+// become -inf.  At a stuck state EOS is written 0.0f, which overrides a min_tokens ban: no row is ever all -inf.
+__global__ void __launch_bounds__(kGuideThreads) sample_guide_mask_kernel(GuideParams p) {
+  const int b = blockIdx.x;
+  int slot, entry, state;
+  if (!guide_row(p, b, &slot, &entry, &state)) return;
+  if ((unsigned)state >= (unsigned)kGuideStates) return;
+  const unsigned short* tab = p.tab + (size_t)entry * kGuideStates * 256;
+  const int flags = p.flags[(size_t)entry * kGuideStates + state];
+  float* row = p.logits + (size_t)b * p.ld;
+  for (int v = threadIdx.x; v < p.V; v += kGuideThreads) {
+    const int g = v + p.vocab_offset;
+    if (g >= p.v_global) { row[v] = -INFINITY; continue; }
+    if (g == p.eos) {
+      if (flags & 2) row[v] = 0.0f;
+      else if (!(flags & 1)) row[v] = -INFINITY;
+    } else if (guide_walk(p, tab, state, g) == kGuideDead) {
+      row[v] = -INFINITY;
+    }
+  }
+}
+
+// After each commit site: state = walk(state, bytes(committed id)).  EOS leaves the state unchanged; a dead walk, or
+// a token of length 0, makes it dead.
+__global__ void sample_guide_advance_kernel(int B, GuideParams p) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int slot, entry, state;
+  if (!guide_row(p, b, &slot, &entry, &state)) return;
+  const int id = DSSE_IDX(p.ids[b], p.v_global, -1);
+  if (id == p.eos) return;
+  int next = kGuideDead;
+  if ((unsigned)state < (unsigned)kGuideStates && (unsigned)id < (unsigned)p.v_global)
+    next = guide_walk(p, p.tab + (size_t)entry * kGuideStates * 256, state, id);
+  p.meta[p.slots + slot] = next;
+}
+
 // The sampled token joins its slot's history (slots with penalties only; a full row drops it: the engine sizes the
 // rows for every token a sequence can sample, max_model_len + 1).
 DEV void hist_append(const int* __restrict__ pen_meta, int Bm, int* __restrict__ hist, int hist_ld, int slot, int id) {
@@ -581,6 +671,36 @@ extern "C" hipError_t dsse_sample_bias_ban(int B, float* logits, const dsse::Sam
       (!p->row_slot && B > p->ctl_slots))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(dsse::sample_bias_ban_kernel, dim3(B), dim3(dsse::kCtlThreads), 0, st, logits, *p);
+  return hipGetLastError();
+}
+
+static bool guide_ok(const dsse::GuideParams* p) {
+  return p->tok_bytes && p->tok_len && p->tab && p->flags && p->meta && p->slots >= 1 && p->pool >= 1 &&
+         p->pool <= dsse::kGuidePool && p->v_global >= 1;
+}
+
+// The stuck bits of pool entry p->entry's states [0, p->n_states).
+extern "C" hipError_t dsse_guide_live(const dsse::GuideParams* p, hipStream_t st) {
+  if (!guide_ok(p) || p->entry < 0 || p->entry >= p->pool || p->n_states < 1 || p->n_states > dsse::kGuideStates)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::guide_live_kernel, dim3(p->n_states), dim3(dsse::kGuideThreads), 0, st, *p);
+  return hipGetLastError();
+}
+
+// Guide mask over logits [B, p->ld] in place.
+extern "C" hipError_t dsse_sample_guide_mask(int B, const dsse::GuideParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (!guide_ok(p) || !p->logits || p->V < 1 || p->ld < p->V || p->vocab_offset < 0 || (!p->row_slot && B > p->slots))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::sample_guide_mask_kernel, dim3(B), dim3(dsse::kGuideThreads), 0, st, *p);
+  return hipGetLastError();
+}
+
+// Guide states of the slots of rows [0, B) advanced by p->ids.
+extern "C" hipError_t dsse_sample_guide_advance(int B, const dsse::GuideParams* p, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (!guide_ok(p) || !p->ids || (!p->row_slot && B > p->slots)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dsse::sample_guide_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, *p);
   return hipGetLastError();
 }
 

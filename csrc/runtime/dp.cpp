@@ -46,6 +46,7 @@ std::string encode_request(const ChatRequest& r) {
   for (int32_t t : r.stop_token_ids) w.i32(t);
   w.i32((int32_t)r.stop.size());
   for (auto& s : r.stop) w.str(s);
+  w.str(r.guide);
   return w.data();
 }
 
@@ -80,6 +81,8 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   n = rd.i32();
   if (n < 0 || n > 4) return false;
   for (int32_t i = 0; i < n && rd.good(); ++i) r->stop.push_back(rd.str());
+  r->guide = rd.str();
+  if (r->guide.size() > 8192) return false;
   return rd.good();
 }
 }  // namespace dpwire

@@ -13,6 +13,7 @@
 
 #include "bus.h"
 #include "dp.h"
+#include "guide.h"
 #include "inspector.h"
 #include "json.h"
 #include "metrics.h"
@@ -48,6 +49,7 @@ py::dict request_dict(const ChatRequest& r) {
   d["stop_token_ids"] = r.stop_token_ids;
   d["min_p"] = r.min_p;
   d["stop"] = r.stop;
+  d["guide"] = r.guide;  // guided_regex, or guided_choice lowered to a pattern; "" = none
   d["from_edge"] = r.from_edge;
   d["messages"] = r.messages_json;
   return d;
@@ -451,4 +453,16 @@ PYBIND11_MODULE(_dsse_runtime, m) {
   m.def("observe_itl", [](double s) { metrics().engine_itl_seconds.observe(s); });
   m.def("set_active_chats", [](double n) { metrics().active_chats.set(n); });
   m.def("uuid4", &uuid4);
+  // guided decoding (guide.h): the pattern compiler the routes validate with and the engine builds its table from
+  m.def("guide_compile", [](const std::string& pattern) {
+    guide::Dfa d;
+    std::string err;
+    if (!guide::compile(pattern, &d, &err)) throw py::value_error(err);
+    return py::make_tuple(d.n_states,
+                          py::bytes(reinterpret_cast<const char*>(d.table.data()), d.table.size() * sizeof(uint16_t)),
+                          py::bytes(reinterpret_cast<const char*>(d.accept.data()), d.accept.size()));
+  }, py::arg("pattern"));
+  m.def("guide_choice_pattern", &guide::choice_pattern, py::arg("choices"));
+  m.attr("GUIDE_STATES") = guide::kGuideStates;
+  m.attr("GUIDE_PATTERN_BYTES") = guide::kGuidePatternBytes;
 }

@@ -1,4 +1,5 @@
 #include "server.h"
+#include "guide.h"
 
 #include <arpa/inet.h>
 #include <fcntl.h>
@@ -322,6 +323,52 @@ bool parse_controls(const std::map<std::string, JsonValue>& o, ChatRequest& r, i
   return true;
 }
 
+// guided_regex / guided_choice of a /chat or /v1/chat/completions body.  Absent or JSON null = not given.  One of
+// them at most, never with ignore_eos (the guide ends a stream through EOS); the pattern must compile (guide.h), so a
+// bad one is a 400 carrying the compiler's message before the stream opens.  r.ignore_eos must already be set.
+bool parse_guide(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err) {
+  auto field = [&](const char* k) -> const JsonValue* {
+    auto it = o.find(k);
+    return (it == o.end() || it->second.kind == JsonValue::kNull) ? nullptr : &it->second;
+  };
+  const JsonValue* re = field("guided_regex");
+  const JsonValue* ch = field("guided_choice");
+  if (!re && !ch) return true;
+  const char* name = re ? "guided_regex" : "guided_choice";
+  if (re && ch) { *err = "guided_regex and guided_choice cannot both be given"; return false; }
+  if (r.ignore_eos) { *err = std::string(name) + " cannot be combined with ignore_eos"; return false; }
+  std::string pattern;
+  if (re) {
+    if (re->kind != JsonValue::kString || re->str.size() > 2048) {
+      *err = "guided_regex must be a string of at most 2048 bytes";
+      return false;
+    }
+    pattern = re->str;
+  } else {
+    const std::string what = "guided_choice must be an array of 1 to 64 distinct strings of 1 to 64 bytes each";
+    std::vector<JsonValue> a;
+    if (ch->kind != JsonValue::kArray || !parse_json_array_of_scalars(ch->raw, a) || a.empty() || a.size() > 64) {
+      *err = what;
+      return false;
+    }
+    std::vector<std::string> choices;
+    for (auto& e : a) {
+      if (e.kind != JsonValue::kString || e.str.empty() || e.str.size() > 64 ||
+          std::find(choices.begin(), choices.end(), e.str) != choices.end()) {
+        *err = what;
+        return false;
+      }
+      choices.push_back(e.str);
+    }
+    pattern = guide::choice_pattern(choices);
+  }
+  guide::Dfa dfa;
+  std::string cerr;
+  if (!guide::compile(pattern, &dfa, &cerr)) { *err = std::string(name) + ": " + cerr; return false; }
+  r.guide = std::move(pattern);
+  return true;
+}
+
 // Optional sampling fields of a /chat body ({message, conversation_id} plus max_tokens, temperature, top_p,
 // top_k, seed, ignore_eos, and the three penalties above). Integers must be integral and in range BEFORE any conversion (a double outside the
 // target type's range is undefined behaviour to cast): false with *err otherwise -> 400.
@@ -358,7 +405,7 @@ bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, s
   r.top_p = top_p;
   auto ie = o.find("ignore_eos");
   r.ignore_eos = ie != o.end() && ie->second.kind == JsonValue::kBool && ie->second.b;
-  return parse_controls(o, r, vocab, err);
+  return parse_controls(o, r, vocab, err) && parse_guide(o, r, err);
 }
 
 std::string http_error(int code, const std::string& msg, bool ka) {
@@ -923,6 +970,8 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   {
     auto ie = o.find("ignore_eos");
     r.ignore_eos = ie != o.end() && ie->second.kind == JsonValue::kBool && ie->second.b;
+    std::string guide_err;
+    if (!parse_guide(o, r, &guide_err)) return bad(400, guide_err);
   }
   {
     // logprobs: bool; top_logprobs: an integer in [0, 20], only with logprobs: true.  The queued request carries

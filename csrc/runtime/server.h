@@ -95,6 +95,9 @@ struct ChatRequest {
   std::vector<int32_t> stop_token_ids;                 // <= 16
   double min_p = 0;                                    // [0, 1]
   std::vector<std::string> stop;                       // <= 4 non-empty strings
+  // guided decoding: guided_regex (<= 2048 bytes), or guided_choice (1..64 distinct strings of 1..64 bytes) lowered
+  // to an alternation of escaped literals; validated with guide::compile before the stream opens.  "" = none
+  std::string guide;
   bool from_edge = false;   // submitted by the edge /chat (a subscriber exists)
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON
   // [{"role":..,"content":..},..]; empty = `message` is a single user turn

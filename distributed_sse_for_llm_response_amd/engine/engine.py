@@ -50,6 +50,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from .. import ops
 from .kv_cache import PAGE, BlockAllocator, blocks_needed
 from .model_runner import PREFILL_GRAPH_SEQS, RING_SIZE, ModelRunner, PrefillSeq, batch_buckets, mixed_mode
 
@@ -83,6 +84,12 @@ class SamplingParams:
     stop_token_ids: tuple = ()
     min_p: float = 0.0
     stop: tuple = ()
+    # guided decoding: one canonical pattern (guided_regex as given, guided_choice lowered to an alternation of escaped
+    # literals) whose full match the delivered text must be, or a prefix of one when max_tokens ends the stream first.
+    # The pattern is compiled to a byte-level DFA (csrc/runtime/guide.cpp) that lives on the device: a mask pass before
+    # the candidates keeps the tokens whose bytes the DFA accepts from the slot's state, an advance pass after the
+    # commit moves the state (sampler.hip sample_guide_mask_kernel / sample_guide_advance_kernel)
+    guide: str | None = None
 
     def penalised(self) -> bool:
         return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
@@ -134,6 +141,7 @@ class Sequence:
     out_ids: list = field(default_factory=list)  # tokens published so far (re-prefilled after a preemption)
     base: int = 0               # tokens published before the latest (re-)admission
     enq_step: int = 0           # engine step at which it was queued (the mixed-step TTFT boost counts steps)
+    guide_entry: int = -1       # pool entry of its pattern while it holds a slot (a reference; -1: none)
 
 
 class EngineFault(RuntimeError):
@@ -345,6 +353,15 @@ class LLMEngine:
         self._pen_live = False  # the device's penalty block holds a non-neutral slot (then _upload rewrites it)
         self._lp_live = False   # the device's lp_meta holds a slot that is on (likewise)
         self._ctl_live = False  # the device's ctl_meta holds a non-neutral slot (likewise)
+        # guided decoding: compiled patterns (pattern -> (table uint16 [n, 256], accept uint8 [n])), and the device
+        # pool's entries: pattern -> index, references by live sequences per index, and the resident pattern per index
+        # (an entry without references stays resident until another pattern needs it)
+        self._guide_dfa: dict = {}
+        self._guide_idx: dict = {}
+        self._guide_refs = [0] * ops.GUIDE_POOL
+        self._guide_pat = [None] * ops.GUIDE_POOL
+        self._guide_lru = 0
+        self._guide_used_at = [0] * ops.GUIDE_POOL
         self.ring_head = int(runner.ring_counter.item()) if runner.device.type == "cuda" else int(runner.ring_counter[0])
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0}
@@ -404,6 +421,10 @@ class LLMEngine:
         """Queue a request.  `rid` (a TP leader's request id, replayed on its followers) seeds the sampling RNG
         when the params carry no seed, so it must be the same on every rank of a TP group."""
         p = params or self.default_params
+        if p.guide is not None:
+            self._guide_compiled(p.guide)  # (ValueError for a pattern the compiler rejects: nothing is queued)
+            if self.r.guide_pieces is None:
+                raise ValueError("guided decoding needs the vocabulary's pieces (ModelRunner.set_guide_vocab)")
         max_prompt = self.r.max_model_len - 1
         if len(prompt) > max_prompt:
             prompt = prompt[-max_prompt:]  # keep the tail (most recent context)
@@ -578,6 +599,43 @@ class LLMEngine:
         ids = ([] if p.ignore_eos else [int(self.eos_id)]) + [int(t) for t in p.stop_token_ids]
         return [t for t in dict.fromkeys(ids) if 0 <= t < V]
 
+    def _guide_compiled(self, pattern: str):
+        """(table, accept) of `pattern`, compiled once (the same compiler the HTTP routes validate with)."""
+        hit = self._guide_dfa.get(pattern)
+        if hit is None:
+            from .. import runtime
+
+            n, tab, acc = runtime.load().guide_compile(pattern)
+            hit = (np.frombuffer(tab, dtype=np.uint16).reshape(n, 256), np.frombuffer(acc, dtype=np.uint8))
+            if len(self._guide_dfa) >= 4 * ops.GUIDE_POOL:  # bounded: drop the oldest
+                self._guide_dfa.pop(next(iter(self._guide_dfa)))
+            self._guide_dfa[pattern] = hit
+        return hit
+
+    def _guide_acquire(self, pattern: str) -> int:
+        """A reference to the pool entry that holds `pattern`, uploading its table into a free entry (one without
+        references, the least recently used) when it is not resident; -1 = every entry is referenced: wait."""
+        e = self._guide_idx.get(pattern, -1)
+        if e < 0:
+            free = [i for i in range(ops.GUIDE_POOL) if self._guide_refs[i] == 0]
+            if not free:
+                return -1
+            e = min(free, key=lambda i: (self._guide_pat[i] is not None, self._guide_used_at[i]))
+            if self._guide_pat[e] is not None:
+                del self._guide_idx[self._guide_pat[e]]
+            tab, acc = self._guide_compiled(pattern)
+            self.r.upload_guide(e, tab, acc)  # (the first one allocates the pool and captures the graph twins)
+            self._guide_pat[e], self._guide_idx[pattern] = pattern, e
+        self._guide_refs[e] += 1
+        self._guide_lru += 1
+        self._guide_used_at[e] = self._guide_lru
+        return e
+
+    def _guide_release(self, s: Sequence) -> None:
+        if s.guide_entry >= 0:
+            self._guide_refs[s.guide_entry] -= 1
+            s.guide_entry = -1
+
     def _victim(self):
         """The sequence to preempt: paused ones first, then the most recent request (FCFS keeps the oldest)."""
         cands = [s for s in self.slots if s is not None and s.state in ("prefill", "decode") and not s.aborted
@@ -596,6 +654,7 @@ class LLMEngine:
                      last_token_ns=v.last_token_ns, paused=v.paused, paused_at=v.paused_at, orig_len=v.orig_len,
                      out_ids=v.out_ids, base=v.produced)
         v.state = "preempted"
+        self._guide_release(v)
         self.slots[v.slot] = None
         self._dirty_slots.add(v.slot)
         self.alloc.free(v.blocks)
@@ -630,6 +689,9 @@ class LLMEngine:
                 max_new = max(1, min(s.params.max_tokens, r.max_model_len - s.orig_len, cap))
                 s.params = SamplingParams(**{**s.params.__dict__, "max_tokens": max_new,
                                              "min_tokens": max(0, min(int(s.params.min_tokens), max_new))})
+            if s.params.guide is not None and s.params.guide not in self._guide_idx and \
+                    all(n > 0 for n in self._guide_refs):
+                return  # its pattern is not resident and every pool entry is in use: it waits, as for KV pages
             need = blocks_needed(len(s.prompt))
             idle = not any(x is not None for x in self.slots)
             if need > self.alloc.num_free - (0 if idle else self.watermark):
@@ -656,6 +718,14 @@ class LLMEngine:
                 # its bias entries and banned ids (again after a preemption: the slot may be another one); the first
                 # such request captures the graph twins with the bias and ban pass and min_p
                 r.set_controls(s.slot, self._bias(s.params), self._ban_ids(s.params))
+            if s.params.guide is not None:
+                # its pattern's pool entry, and the DFA state after the tokens it has already published (after a
+                # preemption the regenerated tokens continue the same match); the device advances it from here on
+                s.guide_entry = self._guide_acquire(s.params.guide)
+                r.set_guide(s.slot, s.guide_entry, ops.guide_walk(self._guide_compiled(s.params.guide)[0], 0, s.out_ids,
+                                                                  *r.guide_host, r.guide_eos))
+            else:
+                r.set_guide(s.slot, -1, 0)  # (a no-op until a guided request has been seen)
 
     def _compact(self):
         """Move decoding sequences above the bucket their count needs into lower free / paused slots."""
@@ -779,6 +849,7 @@ class LLMEngine:
         if s.state == "finished":
             return
         s.state = "finished"
+        self._guide_release(s)
         now = time.time_ns()
         events.append(TokenEvent(s.conversation_id, -1, s.produced + 1, True, text=text, timestamp_ns=now,
                                  finish=reason, prompt_tokens=s.orig_len))

@@ -257,6 +257,13 @@ class ModelRunner:
         self.min_p = self.ctl_meta[3 * Bm:].view(torch.float32)
         self.ctl_body = torch.zeros(Bm, ops.CTL_BODY, **i32)
         self.ctl_used = False  # a request ever used one of them (then the pass is launched / captured)
+        # guided decoding (sampler.hip sample_guide_mask_kernel / sample_guide_advance_kernel; records: api.h): the
+        # token byte table, the pool of transition tables and guide_meta = [pool index (-1 = off) | DFA state] per slot
+        # are allocated by the first guided request (enable_guides), like the twins' buffers
+        self.guide_used = False
+        self.guide_eos = -1
+        self.guide_pieces = None  # the vocabulary's pieces (set_guide_vocab): what the byte table is built from
+        self.tok_bytes = self.tok_len = self.guide_tab = self.guide_flags = self.guide_meta = self.guide_host = None
         # ---- decode activations ----
         bf = dict(device=dev, dtype=torch.bfloat16)
         self.resid = torch.zeros(Bm, H, device=dev, dtype=torch.float32)
@@ -399,6 +406,8 @@ class ModelRunner:
         if self.hist_used:
             ops.sample_penalties(self.logits[r], self.active[r], self.pen_meta, self.hist_state, None,
                                  self.w.vocab_offset, self.cfg.vocab_size)
+        if self.guide_used:  # (same lazy launch / capture) the guide's token mask: last before the candidates
+            self._guide_mask(self.logits[r], self.active[r], None)
         self._candidates(self.logits[r], self.temperature[r], self.top_k[r], self.top_p[r], self.seeds[r],
                          self.positions[r], self.active[r], cand, None)
         if self.comm.size == 1:
@@ -408,6 +417,8 @@ class ModelRunner:
             self.comm.all_gather_into(cand_all, cand)
         ops.sample_pick_hist(cand_all, self.active[r], self.ids[r], self.ring, self.ring_counter, self.positions[r],
                              self.pen_meta, self.hist_state, vocab=self.cfg.vocab_size)
+        if self.guide_used:  # the committed token advances its slot's DFA state
+            self._guide_advance(self.ids[r], self.active[r], None)
         if self.lp_used:  # (before ring_advance: the same ring row the pick wrote)
             self._logprob_finish(self.logits[r], raw, self.ids[r], self.active[r], None, self._lp_bufs[B],
                                  ring_counter=self.ring_counter)
@@ -509,7 +520,71 @@ class ModelRunner:
         self.ctl_body[slot].copy_(row, non_blocking=True)
         self.enable_controls()
 
+    # ------------------------------------------------------------------ guided decoding
+    def set_guide_vocab(self, pieces, eos_id: int) -> None:
+        """The text of every token id (tokenizer.pieces()) and EOS's id: what a guide constrains is the concatenation
+        of piece(id), so the byte table is built from these (at the first guided request)."""
+        self.guide_pieces, self.guide_eos = list(pieces), int(eos_id)
+
+    def enable_guides(self) -> None:
+        """The first guided request: allocate the token byte table (whole on every TP rank), the table pool and
+        guide_meta; from now on every sampling site runs the mask pass before the candidates and the advance pass
+        after the commit (rows without a guide return at once), in graph twins captured here."""
+        if self.guide_used:
+            return
+        if self.guide_pieces is None:
+            raise ValueError("guided decoding needs the vocabulary's pieces (ModelRunner.set_guide_vocab)")
+        V = self.cfg.vocab_size
+        pieces = (self.guide_pieces + [""] * V)[:V]
+        never = {i for i in (0, self.guide_eos) if i >= 0}
+        tb, tl = ops.guide_token_table(pieces, never=never)
+        dev = self.device
+        self.guide_host = (tb, tl)  # (host copies: the engine walks a re-admitted sequence's published tokens)
+        self.tok_bytes, self.tok_len = tb.to(dev), tl.to(dev)
+        self.guide_tab = torch.full((ops.GUIDE_POOL, ops.GUIDE_STATES, 256), -1, device=dev, dtype=torch.int16)
+        self.guide_flags = torch.zeros(ops.GUIDE_POOL, ops.GUIDE_STATES, device=dev, dtype=torch.int32)
+        self.guide_meta = torch.zeros(2 * self.max_batch, device=dev, dtype=torch.int32)
+        self.guide_meta[:self.max_batch] = -1
+        self.guide_used = True
+        self._capture_twins()
+
+    def upload_guide(self, entry: int, table: np.ndarray, accept: np.ndarray) -> None:
+        """Pattern table uint16 [n, 256] (n <= 512) and its accepting flags become pool entry `entry`, stream-ordered
+        after every step already enqueued; then the live pass marks its stuck states."""
+        self.enable_guides()
+        n = int(table.shape[0])
+        if not (1 <= n <= ops.GUIDE_STATES and table.shape[1] == 256 and 0 <= entry < ops.GUIDE_POOL):
+            raise ValueError("guide table must be [1..512, 256]")
+        tab = torch.from_numpy(np.array(table, dtype=np.uint16).view(np.int16))
+        flg = torch.from_numpy(np.ascontiguousarray(accept, dtype=np.int32) & 1)
+        if self.device.type == "cuda":
+            tab, flg = tab.pin_memory(), flg.pin_memory()
+        self.guide_tab[entry, :n].copy_(tab, non_blocking=True)
+        self.guide_flags[entry, :n].copy_(flg, non_blocking=True)
+        ops.guide_live(self.tok_bytes, self.tok_len, self.guide_tab, self.guide_flags, self.guide_meta, entry, n,
+                       self.guide_eos)
+
+    def set_guide(self, slot: int, entry: int, state: int) -> None:
+        """A sequence takes `slot`: its pool entry (-1: no guide) and the DFA state after the tokens it has already
+        published, stream-ordered; from then on the advance pass owns the state."""
+        if not self.guide_used:
+            return
+        m = torch.tensor([entry, state], dtype=torch.int32)
+        if self.device.type == "cuda":
+            m = m.pin_memory()
+        self.guide_meta.view(2, -1)[:, slot].copy_(m, non_blocking=True)
+
+    def _guide_mask(self, logits, active, row_slot) -> None:
+        ops.guide_mask(logits, active, self.tok_bytes, self.tok_len, self.guide_tab, self.guide_flags, self.guide_meta,
+                       row_slot, self.w.vocab_offset, self.guide_eos)
+
+    def _guide_advance(self, ids, active, row_slot) -> None:
+        ops.guide_advance(ids, active, self.tok_bytes, self.tok_len, self.guide_tab, self.guide_flags, self.guide_meta,
+                          row_slot, self.guide_eos)
+
     def _twin_key(self) -> tuple:
+        if self.guide_used:  # the fourth flag: the guide's mask and advance passes
+            return (self.hist_used, self.lp_used, self.ctl_used, True)
         return (self.hist_used, self.lp_used) + ((True,) if self.ctl_used else ())
 
     def _capture_twins(self) -> None:
@@ -554,7 +629,7 @@ class ModelRunner:
         self.twin_capture_s = time.perf_counter() - t0
         if self.comm.rank == 0:
             what = " and ".join(n for n, on in zip(("the penalty pass", "the logprob passes",
-                                                    "the bias and ban pass / min_p"), key) if on)
+                                                    "the bias and ban pass / min_p", "the guide passes"), key) if on)
             print(f"[engine] first request with this combination: captured the graphs with {what} "
                   f"({self.twin_capture_s:.2f} s)", flush=True)
 
@@ -784,6 +859,9 @@ class ModelRunner:
             self.ctl_body.index_copy_(0, di, self.ctl_body.index_select(0, si))
             m = self.ctl_meta.view(4, -1)
             m.index_copy_(1, di, m.index_select(1, si))
+        if self.guide_used:  # the pool index and the device-owned DFA state
+            m = self.guide_meta.view(2, -1)
+            m.index_copy_(1, di, m.index_select(1, si))
 
     def decode(self, B: int) -> None:
         g = self._graph_set()[0].get(B)
@@ -985,7 +1063,8 @@ class ModelRunner:
         sd = self.seeds.index_select(0, slot_idx).contiguous()
         nch = SAMPLE_CHUNKS if dev.type == "cuda" else 1
         cand = torch.zeros(nL, nch, 2, **f32)
-        slot_i32 = slot_idx.to(torch.int32) if self.hist_used or self.lp_used or self.ctl_used else None
+        slot_i32 = slot_idx.to(torch.int32) if self.hist_used or self.lp_used or self.ctl_used or self.guide_used \
+            else None
         if self.lp_used:  # (eager passes: nothing is launched until a request has asked for logprobs / penalties)
             lp_bufs = self._lp_eager_bufs(nL)
             raw = self._logprob_stats(logits, None, slot_i32, lp_bufs)
@@ -996,6 +1075,8 @@ class ModelRunner:
             # after a re-prefill the tokens already published count: the engine uploaded them with the history
             ops.sample_penalties(logits, None, self.pen_meta, self.hist_state, slot_i32, w.vocab_offset,
                                  cfg.vocab_size)
+        if self.guide_used:
+            self._guide_mask(logits, None, slot_i32)
         self._candidates(logits, temp, tk, tp, sd, last_pos, None, cand, slot_i32)
         if comm.size == 1:
             cand_all = cand.unsqueeze(0)
@@ -1007,6 +1088,8 @@ class ModelRunner:
             ops.sample_hist_append(new_ids, slot_i32, None, self.pen_meta, self.hist_state)
         if self.lp_used:
             self._logprob_finish(logits, raw, new_ids, None, slot_i32, lp_bufs, ring_row=ring_row)
+        if self.guide_used:
+            self._guide_advance(new_ids, None, slot_i32)
         self.ids.index_copy_(0, slot_idx, new_ids)
         self.ring[ring_row].index_copy_(0, slot_idx, new_ids)
         self.positions.index_copy_(0, slot_idx, last_pos + 1)
@@ -1083,6 +1166,8 @@ class ModelRunner:
         if self.hist_used:
             ops.sample_penalties(pf.s_logits, active, self.pen_meta, self.hist_state, meta[ns:2 * ns],
                                  w.vocab_offset, cfg.vocab_size)
+        if self.guide_used:
+            self._guide_mask(pf.s_logits, active, meta[ns:2 * ns])
         self._candidates(pf.s_logits, sm[ns:2 * ns].view(torch.float32), sm[2 * ns:3 * ns],
                          sm[3 * ns:4 * ns].view(torch.float32), sm[4 * ns:6 * ns].view(ns, 2), sm[6 * ns:7 * ns],
                          active, pf.s_cand, meta[ns:2 * ns])
@@ -1094,6 +1179,8 @@ class ModelRunner:
         ops.sample_pick(cand_all, active, pf.s_new, vocab=cfg.vocab_size)
         ops.prefill_sample_commit_hist(meta, pf.s_new, self.ids, self.ring, self.positions, self.pen_meta,
                                        self.hist_state)
+        if self.guide_used:
+            self._guide_advance(pf.s_new, active, meta[ns:2 * ns])
         if self.lp_used:
             self._logprob_finish(pf.s_logits, raw, pf.s_new, active, meta[ns:2 * ns], self._lp_pf,
                                  ring_row_dev=meta[3 * ns + 1:3 * ns + 2])

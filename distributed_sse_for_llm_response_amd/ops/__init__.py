@@ -288,6 +288,45 @@ def sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions,
                               ctl_meta, row_slot)
 
 
+# guided decoding: DFA states per pattern / resident patterns / bytes per piece / the dead state (api.h)
+GUIDE_STATES, GUIDE_POOL, GUIDE_TOK_BYTES, GUIDE_DEAD = ref.GUIDE_STATES, ref.GUIDE_POOL, ref.GUIDE_TOK_BYTES, ref.GUIDE_DEAD
+guide_token_table, guide_walk = ref.guide_token_table, ref.guide_walk
+
+
+def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: int, n_states: int, eos: int = -1):
+    """Once per table upload, stream-ordered before first use: bit 1 (stuck) of guide_flags[entry, s], s < n_states =
+    no token of the global vocabulary other than EOS survives from state s."""
+    if _hip(guide_tab):
+        torch.ops.dsse.guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry, n_states, eos)
+    else:
+        ref.guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry, n_states, eos)
+
+
+def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, vocab_offset=0,
+               eos: int = -1):
+    """The guide's token mask, in place on logits [B, V] (row stride >= V): after sample_penalties, immediately before
+    the candidates.  guide_meta int32 [2 slots] = pool index (-1 = off) | DFA state per slot; row b is slot
+    row_slot[b] (else b).  Inactive rows, guide-off slots and dead states keep their logits bit for bit; otherwise a
+    column stays iff its token's bytes walk from the state without meeting dead (EOS: iff accepting or stuck; 0.0 at a
+    stuck state), else -inf."""
+    if _hip(logits):
+        torch.ops.dsse.sample_guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta,
+                                         row_slot, vocab_offset, eos)
+    else:
+        ref.guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, vocab_offset,
+                       eos)
+
+
+def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1):
+    """After a commit: the guide state of row b's slot advances by the committed global id ids[b] (EOS: unchanged; a
+    dead walk or a token of length 0: dead)."""
+    if _hip(guide_meta):
+        torch.ops.dsse.sample_guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta,
+                                            row_slot, eos)
+    else:
+        ref.guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, eos)
+
+
 def sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,
                      vocab: int = 2**31 - 1):
     """sample_pick whose picked token also joins hist[b] (device-side, stream-ordered) where slot b has penalties."""

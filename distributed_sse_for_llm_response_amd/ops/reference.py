@@ -430,6 +430,125 @@ def sample_bias_ban(logits, active, ctl_meta, ctl_body, positions, row_slot=None
                 logits[b, v] = float("-inf")
 
 
+# ---- guided decoding (sampler.hip guide_live_kernel / sample_guide_mask_kernel / sample_guide_advance_kernel) ----
+# tok_bytes uint8 [V_global, GUIDE_TOK_BYTES] / tok_len uint8 [V_global]: the pieces' UTF-8 bytes (length 0 = never
+# allowed under a guide); guide_tab int16 (uint16 bits) [pool, GUIDE_STATES, 256], GUIDE_DEAD = dead; guide_flags int32
+# [pool, GUIDE_STATES]: bit 0 accepting, bit 1 stuck; guide_meta int32 [2 slots] = pool index (-1 = off) | state.
+GUIDE_STATES, GUIDE_POOL, GUIDE_TOK_BYTES, GUIDE_DEAD = 512, 32, 32, 0xFFFF
+
+
+def guide_token_table(pieces, never=()):
+    """(tok_bytes, tok_len) of a vocabulary: the UTF-8 bytes of piece(id).  Length 0 for the ids in `never`, the
+    special pieces <unk> <s> </s>, and any piece that is empty or longer than GUIDE_TOK_BYTES bytes."""
+    V = len(pieces)
+    tb = np.zeros((V, GUIDE_TOK_BYTES), dtype=np.uint8)
+    tl = np.zeros(V, dtype=np.uint8)
+    for i, pc in enumerate(pieces):
+        raw = pc.encode("utf-8") if isinstance(pc, str) else bytes(pc)
+        if i in never or raw in (b"<unk>", b"<s>", b"</s>") or not 1 <= len(raw) <= GUIDE_TOK_BYTES:
+            continue
+        tb[i, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+        tl[i] = len(raw)
+    return torch.from_numpy(tb), torch.from_numpy(tl)
+
+
+def _guide_np(t):
+    return t.detach().cpu().contiguous().numpy()
+
+
+def _guide_walk_all(tab, state: int, tok_bytes, tok_len):
+    """The state every token reaches from `state` (GUIDE_DEAD: none), vectorised over the vocabulary.  tab: uint16
+    [GUIDE_STATES, 256]."""
+    st = np.full(tok_len.shape[0], state, dtype=np.int64)
+    st[(tok_len < 1) | (tok_len > GUIDE_TOK_BYTES)] = GUIDE_DEAD
+    if not 0 <= state < GUIDE_STATES:
+        st[:] = GUIDE_DEAD
+    for j in range(GUIDE_TOK_BYTES):
+        on = (tok_len > j) & (st != GUIDE_DEAD)
+        if not on.any():
+            break
+        nxt = tab[st[on], tok_bytes[on, j]].astype(np.int64)
+        nxt[nxt >= GUIDE_STATES] = GUIDE_DEAD
+        st[on] = nxt
+    return st
+
+
+def guide_walk(table, state: int, ids, tok_bytes, tok_len, eos: int = -1) -> int:
+    """Host walk: the DFA state after the tokens `ids` from `state` (EOS leaves it unchanged; a dead walk, an id
+    outside the vocabulary or a token of length 0 makes it GUIDE_DEAD).  table: uint16 [n_states, 256]."""
+    table, tb, tl = np.asarray(table), _guide_np(tok_bytes), _guide_np(tok_len)
+    for t in ids:
+        t = int(t)
+        if t == eos:
+            continue
+        if not (0 <= state < table.shape[0] and 0 <= t < tl.shape[0] and 1 <= tl[t] <= GUIDE_TOK_BYTES):
+            return GUIDE_DEAD
+        for byte in tb[t, :tl[t]]:
+            state = int(table[state, byte])
+            if state >= min(GUIDE_STATES, table.shape[0]):
+                return GUIDE_DEAD
+    return state
+
+
+def _guide_tab_np(guide_tab, entry: int):
+    return _guide_np(guide_tab[entry]).view(np.uint16)
+
+
+def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: int, n_states: int, eos: int = -1):
+    """Bit 1 of guide_flags[entry, s] for s < n_states: no token of the vocabulary other than EOS survives from s."""
+    tab, tb, tl = _guide_tab_np(guide_tab, entry), _guide_np(tok_bytes), _guide_np(tok_len)
+    for s in range(n_states):
+        alive = _guide_walk_all(tab, s, tb, tl) != GUIDE_DEAD
+        if 0 <= eos < alive.shape[0]:
+            alive[eos] = False
+        guide_flags[entry, s] = (int(guide_flags[entry, s]) & 1) | (0 if alive.any() else 2)
+
+
+def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, vocab_offset=0,
+               eos: int = -1):
+    """In place on logits [B, V] (row b = slot row_slot[b], else b).  Inactive rows, slots with the guide off and
+    slots in the dead state are not touched.  Otherwise column v (global id g = v + vocab_offset) becomes -inf unless
+    g is allowed: EOS iff the state is accepting or stuck, another token iff its bytes walk from the state without
+    meeting dead; at a stuck state EOS becomes 0.0.  Allowed columns keep their bits."""
+    B, V = logits.shape
+    slots = guide_meta.numel() // 2
+    tb, tl = _guide_np(tok_bytes), _guide_np(tok_len)
+    Vg = tl.shape[0]
+    for b in range(B):
+        if active is not None and not int(active[b]):
+            continue
+        slot = int(row_slot[b]) if row_slot is not None else b
+        entry, state = int(guide_meta[slot]), int(guide_meta[slots + slot])
+        if not 0 <= entry < guide_tab.shape[0] or not 0 <= state < GUIDE_STATES:
+            continue
+        flags = int(guide_flags[entry, state])
+        ok = np.zeros(V, dtype=bool)
+        n = max(0, min(V, Vg - vocab_offset))
+        ok[:n] = _guide_walk_all(_guide_tab_np(guide_tab, entry), state, tb[vocab_offset:vocab_offset + n],
+                                 tl[vocab_offset:vocab_offset + n]) != GUIDE_DEAD
+        e = eos - vocab_offset
+        if 0 <= e < n:
+            ok[e] = bool(flags & 3)
+        logits[b, torch.from_numpy(~ok)] = float("-inf")
+        if 0 <= e < n and flags & 2:
+            logits[b, e] = 0.0
+
+
+def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1):
+    """guide_meta's state of row b's slot = walk(state, bytes(ids[b])); EOS leaves it, a dead walk or a token of
+    length 0 makes it GUIDE_DEAD.  Inactive rows and slots with the guide off are skipped."""
+    slots = guide_meta.numel() // 2
+    for b in range(ids.numel()):
+        if active is not None and not int(active[b]):
+            continue
+        slot = int(row_slot[b]) if row_slot is not None else b
+        entry = int(guide_meta[slot])
+        if not 0 <= entry < guide_tab.shape[0] or int(ids[b]) == eos:
+            continue
+        guide_meta[slots + slot] = guide_walk(_guide_tab_np(guide_tab, entry), int(guide_meta[slots + slot]),
+                                              [int(ids[b])], tok_bytes, tok_len, eos)
+
+
 def _hist_append(pen_meta, hist, slot: int, tok: int) -> None:
     if not penalties_on(pen_meta, slot):
         return

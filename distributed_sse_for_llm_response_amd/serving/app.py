@@ -58,6 +58,7 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
                              device=device, comm=comm)
         runner.capture()
     tok = get_tokenizer(mcfg.vocab_size, cfg.tokenizer_path or None)
+    runner.set_guide_vocab(tok.pieces(), tok.eos_id)  # guided decoding constrains the text: the pieces' bytes
     engine = LLMEngine(runner, eos_id=tok.eos_id, prefill_budget=cfg.prefill_budget, max_pause_s=cfg.max_pause_s,
                        default_params=SamplingParams(temperature=cfg.temperature, max_tokens=cfg.max_tokens))
     return engine, tok
@@ -125,7 +126,9 @@ class EngineLoop(threading.Thread):
             # (validated by the HTTP server: <= 300 (id, bias) pairs, <= 16 ids, <= 4 strings)
             logit_bias={int(t): float(b) for t, b in req.get("logit_bias") or ()} or None,
             min_tokens=int(req.get("min_tokens", 0)), stop_token_ids=tuple(int(t) for t in req.get("stop_token_ids") or ()),
-            min_p=float(req.get("min_p", 0.0)), stop=tuple(req.get("stop") or ()))
+            min_p=float(req.get("min_p", 0.0)), stop=tuple(req.get("stop") or ()),
+            # guided_regex, or guided_choice lowered to a pattern (compiled once by the HTTP server to validate it)
+            guide=req.get("guide") or None)
 
     def _watch_stop(self, req, prompt, params: SamplingParams) -> None:
         """A request with stop strings: its events pass through the matcher from now on."""

@@ -71,12 +71,17 @@ class Plan:
                   int(bool(p.ignore_eos)), _f2i(p.temperature), _f2i(p.top_p), _f2i(p.presence_penalty),
                   _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), int(p.logprobs), int(p.min_tokens),
                   _f2i(p.min_p), len(p.logit_bias or ()), len(p.stop_token_ids), len(prompt)]
+            guide = None if p.guide is None else p.guide.encode("utf-8")
+            w[-1:-1] = [-1 if guide is None else len(guide)]  # (before the prompt length) the guide's bytes, -1 = none
             w += [int(t) for t in prompt]
             # variable-length like the prompt: the logit_bias (id, bias bits) pairs, then the stop_token_ids (stop
             # strings stay with the leader: only it has text)
             for t, b in (p.logit_bias or {}).items():
                 w += [int(t), _f2i(b)]
             w += [int(t) for t in p.stop_token_ids]
+            if guide:  # the pattern's UTF-8 bytes, four to an int32 word (little-endian, zero-padded)
+                pad = guide + b"\0" * (-len(guide) % 4)
+                w += [int.from_bytes(pad[i:i + 4], "little", signed=True) for i in range(0, len(pad), 4)]
         for rid in self.aborts:
             w.append(rid)
         for rid, paused in self.flow:
@@ -88,19 +93,25 @@ class Plan:
         p = Plan(step=bool(flags & F_STEP), stop=bool(flags & F_STOP), sync=bool(flags & F_SYNC))
         o = 0
         for _ in range(n_add):
-            rid, a_lo, a_hi, mt, tk, s_lo, s_hi, ie, temp, top_p, pres, freq, rep, lp, mn, min_p, nb, ns, n = w[o:o + 19]
-            o += 19
+            rid, a_lo, a_hi, mt, tk, s_lo, s_hi, ie, temp, top_p, pres, freq, rep, lp, mn, min_p, nb, ns, ng, n = \
+                w[o:o + 20]
+            o += 20
             prompt = w[o:o + n]
             o += n
             bias = {w[o + 2 * j]: _i2f(w[o + 2 * j + 1]) for j in range(nb)}
             o += 2 * nb
             stop_ids = tuple(w[o:o + ns])
             o += ns
+            guide = None
+            if ng >= 0:
+                nw = (ng + 3) // 4
+                guide = b"".join(int(x).to_bytes(4, "little", signed=True) for x in w[o:o + nw])[:ng].decode("utf-8")
+                o += nw
             sp = SamplingParams(temperature=_i2f(temp), top_p=_i2f(top_p), top_k=tk, max_tokens=mt,
                                 seed=None if s_lo < 0 else s_lo | (s_hi << 31), ignore_eos=bool(ie),
                                 presence_penalty=_i2f(pres), frequency_penalty=_i2f(freq),
                                 repetition_penalty=_i2f(rep), logprobs=lp, logit_bias=bias or None, min_tokens=mn,
-                                stop_token_ids=stop_ids, min_p=_i2f(min_p))
+                                stop_token_ids=stop_ids, min_p=_i2f(min_p), guide=guide)
             p.adds.append((rid, prompt, sp, a_lo | (a_hi << 31)))
         for _ in range(n_abort):
             p.aborts.append(w[o])

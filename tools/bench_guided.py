@@ -1,0 +1,125 @@
+"""Cost of guided decoding when used (the numbers of profiles/r10/guided_decoding.md).
+
+    python tools/bench_guided.py [--model mistral-7b] [--streams 64] [--ctx 512] [--reps 100]
+
+1. The mask pass alone at `--streams` rows x V = 32768 over the synthetic vocabulary: every row off, every row at the
+   start of a 512-state pattern that keeps most words alive (long walks), every row in a state that kills every token at
+   its first byte; the live pass of that table; device events around `--reps` back-to-back launches after a warm-up.
+2. The `--streams`-stream decode step of `--model` (random-init weights, garbage KV at `--ctx` tokens of context): the
+   graphs captured at startup, then the lazily captured twins (their one-off capture time is printed) with every
+   stream unguided and with every stream guided by the 512-state pattern (the advance pass moves the states as the
+   step samples).
+One JSON line per measurement.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PATTERN = "[a-z ]{255}[a-z ]{255}[a-z ]"  # 512 states; every lower-case word of the vocabulary survives
+DIGITS = "[0-9]{255}[0-9]{255}[0-9]"      # 512 states; all but ten tokens die at their first byte
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="mistral-7b")
+    ap.add_argument("--streams", type=int, default=64)
+    ap.add_argument("--ctx", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=100)
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    from distributed_sse_for_llm_response_amd import ops, runtime
+    from distributed_sse_for_llm_response_amd.engine.model_runner import ModelRunner
+    from distributed_sse_for_llm_response_amd.engine.weights import random_engine_weights
+    from distributed_sse_for_llm_response_amd.models.mistral import get_config
+    from distributed_sse_for_llm_response_amd.models.tokenizer import SyntheticTokenizer
+
+    ops.load_library(required=True)
+    dev = torch.device("cuda", 0)
+
+    def compiled(pattern):
+        n, tab, acc = runtime.load().guide_compile(pattern)
+        return np.frombuffer(tab, dtype=np.uint16).reshape(n, 256), np.frombuffer(acc, dtype=np.uint8)
+
+    def timed_us(fn, n=a.reps, warm=10):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(n):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return round(t0.elapsed_time(t1) / n * 1e3, 1)
+
+    cfg = get_config(a.model)
+    tok = SyntheticTokenizer(cfg.vocab_size)
+    w = random_engine_weights(cfg, device=dev, seed=0)
+    B = a.streams
+    pages = a.ctx // 32 + 2
+    r = ModelRunner(w, num_blocks=B * pages + 8, max_batch=B, max_model_len=a.ctx + 64, device=dev)
+    r.set_guide_vocab(tok.pieces(), tok.eos_id)
+    for s in range(B):
+        r.block_tables[s, :pages] = torch.arange(pages * s, pages * (s + 1), dtype=torch.int32)
+    r.active.fill_(1)
+    r.capture([B])
+
+    def step_us():
+        r.positions.fill_(a.ctx)  # (every replay advances the positions: keep the context fixed)
+        return timed_us(lambda: r.decode(B), warm=5, n=min(a.reps, 50))
+
+    out = {"what": "decode step", "model": cfg.name, "streams": B, "ctx": a.ctx, "V_local": w.vocab_local,
+           "startup_graphs_us": step_us()}
+    r.temperature.fill_(1.0)  # (guided streams sample: their baseline is the sampling step)
+    out["startup_graphs_temperature_1_us"] = step_us()
+    r.enable_guides()
+    out["twin_capture_s"] = round(r.twin_capture_s, 2)
+    out["twins_all_unguided_us"] = step_us()
+    r.upload_guide(0, *compiled(PATTERN))
+    r.upload_guide(1, *compiled(DIGITS))
+
+    def guide_all(entry, state=0):
+        m = torch.zeros(2 * B, dtype=torch.int32)
+        m[:B], m[B:] = entry, state
+        r.guide_meta.copy_(m)
+
+    # the mask pass alone, on the runner's own tables
+    x = (torch.randn(B, cfg.vocab_size, device=dev) * 4).clamp_(-32, 32)
+    alone = {"what": "mask pass alone", "rows": B, "V": cfg.vocab_size}
+    guide_all(-1)
+    alone["all_off_us"] = timed_us(lambda: r._guide_mask(x, None, None))
+    guide_all(0)
+    alone["all_words_survive_us"] = timed_us(lambda: r._guide_mask(x.copy_(x.clamp(min=-32)), None, None))
+    alone["row_restore_alone_us"] = timed_us(lambda: x.copy_(x.clamp(min=-32)))
+    guide_all(1)
+    alone["all_die_at_first_byte_us"] = timed_us(lambda: r._guide_mask(x, None, None))
+    alone["live_pass_512_states_us"] = timed_us(
+        lambda: ops.guide_live(r.tok_bytes, r.tok_len, r.guide_tab, r.guide_flags, r.guide_meta, 0, 512, r.guide_eos),
+        n=10, warm=2)
+    print(json.dumps(alone), flush=True)
+
+    def guided_step_us(entry):
+        def fn():
+            guide_all(entry)  # (back to the start state: the advance pass moved it)
+            r.decode(B)
+        r.positions.fill_(a.ctx)
+        return timed_us(fn, warm=5, n=min(a.reps, 50))
+
+    out["twins_all_guided_words_us"] = guided_step_us(0)
+    out["twins_all_guided_digits_us"] = guided_step_us(1)
+    guide_all(-1)
+    out["twins_all_unguided_with_meta_upload_us"] = guided_step_us(-1)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
