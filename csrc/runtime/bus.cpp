@@ -26,6 +26,7 @@ FramePtr Bus::make_frame(const TokenMessage& m) {
   f->timestamp = m.timestamp;
   f->finish = m.finish;
   f->prompt_tokens = m.prompt_tokens;
+  f->cached_tokens = m.cached_tokens;
   f->logprobs = m.logprobs;
   f->created_mono = mono_ns();
   char head[48];

@@ -47,6 +47,7 @@ struct Frame {
   int64_t timestamp = 0;
   uint8_t finish = kFinishNone;  // TokenMessage::finish
   int32_t prompt_tokens = -1;
+  int32_t cached_tokens = -1;    // TokenMessage::cached_tokens
   std::string logprobs;          // TokenMessage::logprobs (the OpenAI route's entry; never part of `bytes`)
   int64_t created_mono = 0;      // formatting time (dedupe window clock)
 };

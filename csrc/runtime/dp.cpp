@@ -168,7 +168,29 @@ std::vector<DpWorkerInfo> DpRouter::workers() {
   return info_;
 }
 
-int DpRouter::pick_worker_locked(const std::string& conv_id) {
+uint64_t dp_affinity_key(const std::string& s) {
+  // objects of the server's normalised form: {"role":"<role>","content":"<json string>"}
+  static const std::string kRole = "{\"role\":\"", kContent = "\",\"content\":\"";
+  size_t end = s.size();
+  size_t p = s.empty() || s[0] != '[' ? std::string::npos : 1;
+  while (p != std::string::npos && s.compare(p, kRole.size(), kRole) == 0) {
+    const size_t role0 = p + kRole.size(), role1 = s.find('"', role0);
+    if (role1 == std::string::npos || s.compare(role1, kContent.size(), kContent) != 0) break;
+    size_t q = role1 + kContent.size();
+    while (q < s.size() && s[q] != '"') q += s[q] == '\\' ? 2 : 1;  // the content string, escapes skipped
+    if (q + 1 >= s.size() || s[q + 1] != '}') break;
+    if (s.compare(role0, role1 - role0, "user") == 0) {
+      end = q + 2;
+      break;
+    }
+    p = s[q + 2] == ',' ? q + 3 : std::string::npos;
+  }
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < end; ++i) h = (h ^ (uint8_t)s[i]) * 1099511628211ull;
+  return h;
+}
+
+int DpRouter::pick_worker_locked(const std::string& conv_id, const std::string& messages_json) {
   auto it = convs_.find(conv_id);
   if (it != convs_.end() && it->second.worker >= 0 && info_[(size_t)it->second.worker].alive) return it->second.worker;
   // least outstanding; ties rotate (a low request rate would otherwise always land on the lowest index)
@@ -179,12 +201,20 @@ int DpRouter::pick_worker_locked(const std::string& conv_id) {
     if (!i.ready || !i.alive) continue;
     if (best < 0 || i.outstanding < info_[(size_t)best].outstanding) best = w;
   }
+  // prefix-cache affinity: the conversation's worker, unless it is loaded past the slack (then, as for every /chat
+  // request and with the feature off, the policy above).  The rotation moves only when that policy chose.
+  const int slack = affinity_slack_.load(std::memory_order_relaxed);
+  if (best >= 0 && slack >= 0 && !messages_json.empty()) {
+    const int a = (int)(dp_affinity_key(messages_json) % (uint64_t)n_);
+    const auto& i = info_[(size_t)a];
+    if (i.ready && i.alive && i.outstanding <= info_[(size_t)best].outstanding + slack) return a;
+  }
   if (best >= 0) rr_ = (best + 1) % n_;
   return best;
 }
 
 bool DpRouter::send_request_locked(ChatRequest r) {
-  const int w = pick_worker_locked(r.conversation_id);
+  const int w = pick_worker_locked(r.conversation_id, r.messages_json);
   if (w < 0) return false;
   const std::string msg = dpwire::encode_request(r);
   if (!to_w_[(size_t)w]->push_wait(msg.data(), (uint32_t)msg.size(), 1000)) return false;
@@ -294,6 +324,7 @@ void DpRouter::handle_tokens(int w, dpwire::Reader& rd) {
     m.finish = rd.u8();
     m.prompt_tokens = rd.i32();
     m.logprobs = rd.str();
+    m.cached_tokens = rd.i32();
     if (!text.empty()) m.token = std::move(text);
     else if (tok >= 0 && (size_t)tok < vocab->size()) m.token = (*vocab)[(size_t)tok];
     else m.token = "<" + std::to_string(tok) + ">";
@@ -343,6 +374,11 @@ void DpRouter::drain_loop(int w) {
       for (int32_t k = 0; k < ni && rd.good(); ++k) metrics().engine_itl_seconds.observe(rd.f64());
       const int32_t nh = rd.good() ? rd.i32() : 0;
       for (int32_t k = 0; k < nh && rd.good(); ++k) metrics().engine_host_step_seconds.observe(rd.f64());
+      const int32_t np = rd.good() ? rd.i32() : 0;
+      if (np == 3 && rd.good()) {
+        const double q = rd.f64(), h = rd.f64(), e = rd.f64();
+        if (rd.good()) metrics().observe_prefix_cache(q, h, e);
+      }
       if (step_s > 0) metrics().engine_decode_step_seconds.observe(step_s);
       double batch = 0, kv = 0, active = 0;
       for (auto& x : info_) {
@@ -409,7 +445,8 @@ std::vector<ChatRequest> DpWorker::poll(size_t max, int timeout_ms, std::vector<
 bool DpWorker::publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                               const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                               const std::vector<std::string>& texts, const std::vector<int>& finish,
-                              const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs) {
+                              const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs,
+                              const std::vector<int>& cached_tokens) {
   const size_t n = conv_ids.size();
   dpwire::Writer m;
   m.u8(dpwire::kTokens);
@@ -425,6 +462,7 @@ bool DpWorker::publish_tokens(const std::vector<std::string>& conv_ids, const st
     m.u8(i < finish.size() ? (uint8_t)finish[i] : 0);
     m.i32(i < prompt_tokens.size() ? prompt_tokens[i] : -1);
     m.str(i < logprobs.size() ? logprobs[i] : empty);
+    m.i32(i < cached_tokens.size() ? cached_tokens[i] : -1);
   }
   return send(m.data());
 }
@@ -443,7 +481,8 @@ void DpWorker::bye() {
 }
 
 void DpWorker::stats(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,
-                     const std::vector<double>& itl, const std::vector<double>& host) {
+                     const std::vector<double>& itl, const std::vector<double>& host,
+                     const std::vector<double>& prefix) {
   dpwire::Writer m;
   m.u8(dpwire::kStats);
   m.f64(step_s);
@@ -456,6 +495,9 @@ void DpWorker::stats(double step_s, double batch, double kv_free, double active,
   for (double v : itl) m.f64(v);
   m.i32((int32_t)host.size());
   for (double v : host) m.f64(v);
+  // prefix caching on: [queries, hits, evictions] since the last message (empty: the feature is off)
+  m.i32((int32_t)prefix.size());
+  for (double v : prefix) m.f64(v);
   send(m.data());
 }
 

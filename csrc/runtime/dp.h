@@ -94,6 +94,11 @@ struct DpWorkerInfo {
   double batch = 0, kv_free = 0, active = 0;
 };
 
+// Affinity key of an OpenAI chat request: FNV-1a of the normalised messages ([{"role":..,"content":..},..], as the
+// server writes them) up to and including the first user message -- the same on every turn of one conversation,
+// whatever follows.  Without a user message (or if the text is not in that form): of the whole string.
+uint64_t dp_affinity_key(const std::string& messages_json);
+
 class DpRouter {
  public:
   DpRouter(Server& server, std::string prefix, int workers, size_t ring_bytes = 8 << 20, int worker_timeout_ms = 10000);
@@ -103,6 +108,11 @@ class DpRouter {
   void set_vocab(std::vector<std::string> pieces);
   std::vector<DpWorkerInfo> workers();
   int num_workers() const { return n_; }
+  // Prefix-cache affinity (off by default: slack < 0).  With the engines' prefix caching on, an OpenAI chat request
+  // (messages_json) prefers worker dp_affinity_key(messages) % n -- where the earlier turns of its conversation
+  // left their KV pages -- as long as that worker's outstanding count is at most the least outstanding count plus
+  // `slack`; otherwise, and for /chat requests, the least-outstanding policy applies unchanged.
+  void set_prefix_affinity(int slack) { affinity_slack_ = slack; }
 
  private:
   struct Conv {
@@ -112,7 +122,7 @@ class DpRouter {
   };
   void dispatch_loop();
   void drain_loop(int w);
-  int pick_worker_locked(const std::string& conv_id);
+  int pick_worker_locked(const std::string& conv_id, const std::string& messages_json);
   bool send_request_locked(ChatRequest r);
   void check_liveness_locked(int64_t now_ms);
   void handle_tokens(int w, dpwire::Reader& rd);
@@ -124,6 +134,7 @@ class DpRouter {
   int rr_ = 0;  // first worker examined by the next pick: ties on outstanding rotate over the replicas
   size_t ring_bytes_;
   int timeout_ms_;
+  std::atomic<int> affinity_slack_{-1};
   std::vector<std::unique_ptr<ShmRing>> to_w_, from_w_;
   std::mutex mu_;
   std::vector<DpWorkerInfo> info_;
@@ -150,11 +161,12 @@ class DpWorker {
                       const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                       const std::vector<std::string>& texts, const std::vector<int>& finish = {},
                       const std::vector<int>& prompt_tokens = {},
-                      const std::vector<std::string>& logprobs = {});
+                      const std::vector<std::string>& logprobs = {}, const std::vector<int>& cached_tokens = {});
   void hello();
   void bye();
   void stats(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,
-             const std::vector<double>& itl, const std::vector<double>& host = {});
+             const std::vector<double>& itl, const std::vector<double>& host = {},
+             const std::vector<double>& prefix = {});
 
  private:
   void heartbeat_if_due();

@@ -30,6 +30,9 @@ struct TokenMessage {
   // OpenAI logprobs entry of this token, ready-made JSON ({"token":..,"logprob":..,"bytes":[..],"top_logprobs":[..]});
   // empty = none.  Like finish / prompt_tokens it rides along in the Frame, outside the wire JSON.
   std::string logprobs;
+  // terminal messages of an engine with prefix caching on: prompt tokens served from resident KV pages (-1 = the
+  // feature is off, or unknown).  Rides beside prompt_tokens, outside the wire JSON.
+  int32_t cached_tokens = -1;
 };
 
 // Append a JSON string literal (with quotes) using Go json.Marshal escaping rules.

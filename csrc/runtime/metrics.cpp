@@ -132,6 +132,15 @@ std::string Metrics::render() const {
   hist(o, "engine_itl_seconds", "Inter-token latency", engine_itl_seconds);
   hist(o, "engine_host_step_seconds", "Host time of an engine step (scheduling, launches, token processing; drain waits excluded)",
        engine_host_step_seconds);
+  if (prefix_cache_on.load(std::memory_order_relaxed) || engine_prefix_cache_queries_total.get() > 0 ||
+      engine_prefix_cache_hits_total.get() > 0 || engine_prefix_cache_evictions_total.get() > 0) {
+    line(o, "engine_prefix_cache_queries_total", "Prompt tokens looked up in the prefix cache at admission", "counter",
+         engine_prefix_cache_queries_total.get());
+    line(o, "engine_prefix_cache_hits_total", "Prompt tokens served from resident KV pages", "counter",
+         engine_prefix_cache_hits_total.get());
+    line(o, "engine_prefix_cache_evictions_total", "KV pages evicted from the prefix cache", "counter",
+         engine_prefix_cache_evictions_total.get());
+  }
   line(o, "dp_workers_alive", "Data-parallel engine workers with a live heartbeat", "gauge", dp_workers_alive.get());
   line(o, "dp_requests_routed_total", "Chat requests routed to data-parallel engine workers", "counter",
        dp_requests_routed_total.get());

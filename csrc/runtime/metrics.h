@@ -84,6 +84,19 @@ class Metrics {
   Histogram engine_ttft_seconds;
   Histogram engine_itl_seconds;
   Histogram engine_host_step_seconds;  // host (Python + launch) time of an engine step, drain waits excluded
+  // automatic prefix caching (engine/kv_cache.py): prompt tokens looked up at admission, prompt tokens served from
+  // resident KV pages (vLLM's meaning of both), pages evicted from the cache.  Rendered only when non-zero or when an
+  // engine with the feature on has reported (observe_prefix_cache).
+  Counter engine_prefix_cache_queries_total;
+  Counter engine_prefix_cache_hits_total;
+  Counter engine_prefix_cache_evictions_total;
+  std::atomic<bool> prefix_cache_on{false};
+  void observe_prefix_cache(double queries, double hits, double evictions) {
+    prefix_cache_on.store(true, std::memory_order_relaxed);
+    if (queries > 0) engine_prefix_cache_queries_total.add(queries);
+    if (hits > 0) engine_prefix_cache_hits_total.add(hits);
+    if (evictions > 0) engine_prefix_cache_evictions_total.add(evictions);
+  }
   // data-parallel router (dp.h)
   Gauge dp_workers_alive;
   Counter dp_requests_routed_total;

@@ -138,9 +138,11 @@ class Runtime {
   }
 
   // Data-parallel mode: this runtime becomes the router for `workers` engine processes (dp.h).
-  void start_dp_router(const std::string& prefix, int workers, int ring_mb, int worker_timeout_ms) {
+  void start_dp_router(const std::string& prefix, int workers, int ring_mb, int worker_timeout_ms,
+                       int prefix_affinity_slack) {
     dp_ = std::make_unique<DpRouter>(*server_, prefix, workers, (size_t)ring_mb << 20, worker_timeout_ms);
     dp_->set_vocab(vocab_);
+    dp_->set_prefix_affinity(prefix_affinity_slack);  // (< 0: off, the default)
     std::string err;
     if (!dp_->start(&err)) {
       dp_.reset();
@@ -168,7 +170,8 @@ class Runtime {
   int publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                      const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                      const std::vector<std::string>& texts, const std::vector<int>& finish,
-                     const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs) {
+                     const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs,
+                     const std::vector<int>& cached_tokens) {
     const size_t n = conv_ids.size();
     if (token_ids.size() != n || seqs.size() != n || dones.size() != n)
       throw std::invalid_argument("publish_tokens: length mismatch");
@@ -190,6 +193,7 @@ class Runtime {
         m.prompt_tokens = i < prompt_tokens.size() ? prompt_tokens[i] : -1;
         if (i < logprobs.size()) m.logprobs = logprobs[i];
         else m.logprobs.clear();
+        m.cached_tokens = i < cached_tokens.size() ? cached_tokens[i] : -1;
         frames.push_back(Bus::make_frame(m));
       }
       bus_->publish_batch(frames);
@@ -262,12 +266,13 @@ class DpWorkerPy {
   int publish_tokens(const std::vector<std::string>& conv_ids, const std::vector<int>& token_ids,
                      const std::vector<int64_t>& seqs, const std::vector<bool>& dones, int64_t ts,
                      const std::vector<std::string>& texts, const std::vector<int>& finish,
-                     const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs) {
+                     const std::vector<int>& prompt_tokens, const std::vector<std::string>& logprobs,
+                     const std::vector<int>& cached_tokens) {
     const size_t n = conv_ids.size();
     if (token_ids.size() != n || seqs.size() != n || dones.size() != n)
       throw std::invalid_argument("publish_tokens: length mismatch");
     py::gil_scoped_release nogil;
-    if (!w_->publish_tokens(conv_ids, token_ids, seqs, dones, ts, texts, finish, prompt_tokens, logprobs))
+    if (!w_->publish_tokens(conv_ids, token_ids, seqs, dones, ts, texts, finish, prompt_tokens, logprobs, cached_tokens))
       throw std::runtime_error("dp worker: token ring closed or full");
     return (int)n;
   }
@@ -277,9 +282,9 @@ class DpWorkerPy {
     else w_->bye();
   }
   void observe(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,
-               const std::vector<double>& itl, const std::vector<double>& host) {
+               const std::vector<double>& itl, const std::vector<double>& host, const std::vector<double>& prefix) {
     py::gil_scoped_release nogil;
-    w_->stats(step_s, batch, kv_free, active, ttft, itl, host);
+    w_->stats(step_s, batch, kv_free, active, ttft, itl, host, prefix);
   }
   void set_vocab(const std::vector<std::string>&) {}  // text is resolved by the router
 
@@ -371,7 +376,8 @@ PYBIND11_MODULE(_dsse_runtime, m) {
       .def("publish_tokens", &Runtime::publish_tokens, py::arg("conversation_ids"), py::arg("token_ids"),
            py::arg("sequences"), py::arg("dones"), py::arg("timestamp_ns") = 0,
            py::arg("texts") = std::vector<std::string>{}, py::arg("finish") = std::vector<int>{},
-           py::arg("prompt_tokens") = std::vector<int>{}, py::arg("logprobs") = std::vector<std::string>{})
+           py::arg("prompt_tokens") = std::vector<int>{}, py::arg("logprobs") = std::vector<std::string>{},
+           py::arg("cached_tokens") = std::vector<int>{})
       .def("publish", &Runtime::publish, py::arg("conversation_id"), py::arg("token"), py::arg("sequence"),
            py::arg("done") = false, py::arg("timestamp_ns") = 0)
       .def("pop_cancellations", &Runtime::pop_cancellations)
@@ -384,8 +390,9 @@ PYBIND11_MODULE(_dsse_runtime, m) {
       .def("start_stub", &Runtime::start_stub, py::arg("tokens") = 50, py::arg("delay_ms") = 50, py::arg("workers") = 2)
       .def("metrics_text", &Runtime::metrics_text)
       .def("start_dp_router", &Runtime::start_dp_router, py::arg("prefix"), py::arg("workers"), py::arg("ring_mb") = 8,
-           py::arg("worker_timeout_ms") = 10000)
+           py::arg("worker_timeout_ms") = 10000, py::arg("prefix_affinity_slack") = -1)
       .def("dp_workers", &Runtime::dp_workers);
+  m.def("dp_affinity_key", &dp_affinity_key, py::arg("messages_json"));
 
   py::class_<DpWorkerPy>(m, "DpWorker")
       .def(py::init<const std::string&, int, int>(), py::arg("prefix"), py::arg("worker"),
@@ -397,10 +404,12 @@ PYBIND11_MODULE(_dsse_runtime, m) {
       .def("publish_tokens", &DpWorkerPy::publish_tokens, py::arg("conversation_ids"), py::arg("token_ids"),
            py::arg("sequences"), py::arg("dones"), py::arg("timestamp_ns") = 0,
            py::arg("texts") = std::vector<std::string>{}, py::arg("finish") = std::vector<int>{},
-           py::arg("prompt_tokens") = std::vector<int>{}, py::arg("logprobs") = std::vector<std::string>{})
+           py::arg("prompt_tokens") = std::vector<int>{}, py::arg("logprobs") = std::vector<std::string>{},
+           py::arg("cached_tokens") = std::vector<int>{})
       .def("set_ready", &DpWorkerPy::set_ready)
       .def("observe", &DpWorkerPy::observe, py::arg("step_s"), py::arg("batch"), py::arg("kv_free"), py::arg("active"),
-           py::arg("ttft"), py::arg("itl"), py::arg("host") = std::vector<double>{})
+           py::arg("ttft"), py::arg("itl"), py::arg("host") = std::vector<double>{},
+           py::arg("prefix") = std::vector<double>{})
       .def("set_vocab", &DpWorkerPy::set_vocab);
   m.def("dp_ring_name", &dp_ring_name);
 
@@ -450,6 +459,10 @@ PYBIND11_MODULE(_dsse_runtime, m) {
     metrics().engine_kv_blocks_free.set(kv_free);
   }, py::arg("step_s"), py::arg("batch"), py::arg("kv_free"), py::arg("host_s") = -1.0);
   m.def("observe_ttft", [](double s) { metrics().engine_ttft_seconds.observe(s); });
+  // prefix caching on: deltas since the last call (the first call, even of zeros, makes /metrics show the counters)
+  m.def("observe_prefix_cache", [](double queries, double hits, double evictions) {
+    metrics().observe_prefix_cache(queries, hits, evictions);
+  }, py::arg("queries"), py::arg("hits"), py::arg("evictions"));
   m.def("observe_itl", [](double s) { metrics().engine_itl_seconds.observe(s); });
   m.def("set_active_chats", [](double n) { metrics().active_chats.set(n); });
   m.def("uuid4", &uuid4);

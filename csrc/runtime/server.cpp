@@ -588,7 +588,7 @@ class IoThread {
   void deliver_token(Conn& c, const FramePtr& f);
   void handle_openai(Conn& c, HttpRequest& req);
   void deliver_openai(Conn& c, const FramePtr& f);
-  void finish_openai(Conn& c, const char* finish_reason, int prompt_tokens = -1);
+  void finish_openai(Conn& c, const char* finish_reason, int prompt_tokens = -1, int cached_tokens = -1);
   void flush_out(Conn& c);
   void close_conn(Conn& c);
   void drain_outbox();
@@ -1043,7 +1043,7 @@ void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
     else if (f->finish == kFinishLength) reason = "length";
     else if (f->finish == kFinishAbort || m.token == "[ERROR]" || m.token == "[BLOCKED]" || m.token == "[KILLED]") reason = "abort";
     else reason = c.oa_max_tokens > 0 && c.oa_count >= c.oa_max_tokens ? "length" : "stop";
-    return finish_openai(c, reason, f->prompt_tokens);
+    return finish_openai(c, reason, f->prompt_tokens, f->cached_tokens);
   }
   c.got_first = true;
   ++c.oa_count;
@@ -1075,17 +1075,24 @@ void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
   write_sse_bytes(c, ev);
 }
 
-void IoThread::finish_openai(Conn& c, const char* finish_reason, int prompt_tokens) {
+void IoThread::finish_openai(Conn& c, const char* finish_reason, int prompt_tokens, int cached_tokens) {
   if (!c.sse) return;
   const int pt = std::max(0, prompt_tokens);
   const std::string head = "{\"id\":" + json_quote(c.conv_id) + ",\"object\":\"chat.completion" +
                            std::string(c.oa_stream ? ".chunk" : "") + "\",\"created\":" + std::to_string(c.oa_created) +
                            ",\"model\":" + json_quote(c.oa_model) + ",\"choices\":[{\"index\":0,";
   const std::string usage = "\"usage\":{\"prompt_tokens\":" + std::to_string(pt) + ",\"total_tokens\":" +
-                            std::to_string(pt + c.oa_count) + ",\"completion_tokens\":" + std::to_string(c.oa_count) + "}";
+                            std::to_string(pt + c.oa_count) + ",\"completion_tokens\":" + std::to_string(c.oa_count) +
+                            // prefix caching on (the engine then sends a count >= 0): vLLM's prompt_tokens_details;
+                            // off: no such key, and the stream's last chunk carries no usage, as before
+                            (cached_tokens >= 0 ? ",\"prompt_tokens_details\":{\"cached_tokens\":" +
+                                                      std::to_string(cached_tokens) + "}"
+                                                : std::string()) +
+                            "}";
   if (c.oa_stream) {
     std::string ev = "data: " + head + "\"delta\":{},\"logprobs\":null,\"finish_reason\":\"" + finish_reason +
-                     "\",\"stop_reason\":null}]}\n\ndata: [DONE]\n\n";
+                     "\",\"stop_reason\":null}]" + (cached_tokens >= 0 ? "," + usage : std::string()) +
+                     "}\n\ndata: [DONE]\n\n";
     append_chunk(c.out, ev.data(), ev.size());
     end_sse(c, true);
     return;
@@ -1921,6 +1928,7 @@ FramePtr with_token(const FramePtr& f, const std::string& token) {
   m.token = token;
   m.finish = f->finish;
   m.prompt_tokens = f->prompt_tokens;
+  m.cached_tokens = f->cached_tokens;
   // (the logprobs entry is NOT carried over: it names the original piece, its bytes and the alternatives, which is
   // what the inspector hid; a replaced token reports no logprobs)
   return Bus::make_frame(m);

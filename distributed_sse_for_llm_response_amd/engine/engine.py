@@ -51,7 +51,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .kv_cache import PAGE, BlockAllocator, blocks_needed
+from .kv_cache import PAGE, BlockAllocator, blocks_needed, page_hashes
 from .model_runner import PREFILL_GRAPH_SEQS, RING_SIZE, ModelRunner, PrefillSeq, batch_buckets, mixed_mode
 
 
@@ -114,6 +114,7 @@ class TokenEvent:
     prompt_tokens: int = -1  # terminal events: prompt length (OpenAI usage)
     logprob: float | None = None  # streams that asked for logprobs: the sampled token's raw logprob ...
     top: list | None = None       # ... and the top N as [(token id, logprob)], logit descending, ties by ascending id
+    cached_tokens: int = -1  # terminal events, prefix caching on: prompt tokens whose KV was reused (else -1)
 
 
 @dataclass
@@ -142,6 +143,10 @@ class Sequence:
     base: int = 0               # tokens published before the latest (re-)admission
     enq_step: int = 0           # engine step at which it was queued (the mixed-step TTFT boost counts steps)
     guide_entry: int = -1       # pool entry of its pattern while it holds a slot (a reference; -1: none)
+    stamped: bool = False       # admit_ns was taken (its first chunk was planned; a cache hit never has prefilled == 0)
+    cached_tokens: int = -1     # prefix caching: prompt tokens served from resident pages at its FIRST admission
+    hashes: list = field(default_factory=list)  # prefix caching: chain hashes of its full pages, prompt pages first
+    published: int = 0          # prefix caching: its leading pages that are shared or were offered to the index
 
 
 class EngineFault(RuntimeError):
@@ -323,10 +328,19 @@ class PassCost:
 class LLMEngine:
     def __init__(self, runner: ModelRunner, eos_id: int = 2, prefill_budget: int = 512,
                  idle_prefill_budget: int | None = None, default_params: SamplingParams | None = None,
-                 pipeline_depth: int | None = None, max_pause_s: float = 30.0, deterministic: bool | None = None):
+                 pipeline_depth: int | None = None, max_pause_s: float = 30.0, deterministic: bool | None = None,
+                 prefix_cache: bool = False):
         self.r = runner
         self.eos_id = eos_id
-        self.alloc = BlockAllocator(runner.kv.num_blocks)
+        # automatic prefix caching (off by default): full KV pages are indexed by the hash of the token prefix they
+        # end, and a prompt that starts with resident pages shares them and prefills only the rest (_admit).  Every
+        # rank of a TP group runs this same allocator on the same inputs in the same order (the plan carries requests,
+        # not pages; drained steps are consumed by count), so block tables and start positions agree without
+        # travelling.
+        self.prefix_cache = bool(prefix_cache)
+        self.alloc = BlockAllocator(runner.kv.num_blocks, prefix_cache=self.prefix_cache)
+        self.shared_write_violations = 0  # a step's write slots named a shared page (checked when debug_shared_writes)
+        self.debug_shared_writes = runner.device.type != "cuda" or os.environ.get("DSSE_DEBUG_PREFIX_CACHE", "0") == "1"
         self.prefill_budget = prefill_budget
         self.idle_prefill_budget = idle_prefill_budget or runner.max_prefill_tokens
         self.default_params = default_params or SamplingParams()
@@ -364,7 +378,9 @@ class LLMEngine:
         self._guide_used_at = [0] * ops.GUIDE_POOL
         self.ring_head = int(runner.ring_counter.item()) if runner.device.type == "cuda" else int(runner.ring_counter[0])
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
-                      "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0}
+                      "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0,
+                      # prefix caching: prompt tokens looked up / served from resident pages (admissions), pages evicted
+                      "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0}
         # admission keeps this many pages free for running sequences to grow into (vLLM's 1% watermark)
         self.watermark = max(1, runner.kv.num_blocks // 100)
         self._bt_new: list = []  # (sequence, page index, block) appended since the last upload
@@ -652,7 +668,10 @@ class LLMEngine:
         n = Sequence(rid=v.rid, conversation_id=v.conversation_id, prompt=v.prompt[:v.orig_len] + v.out_ids,
                      params=v.params, arrival_ns=v.arrival_ns, produced=v.produced, first_token_ns=v.first_token_ns,
                      last_token_ns=v.last_token_ns, paused=v.paused, paused_at=v.paused_at, orig_len=v.orig_len,
-                     out_ids=v.out_ids, base=v.produced)
+                     out_ids=v.out_ids, base=v.produced, cached_tokens=v.cached_tokens)
+        # prefix caching: no special case.  Its full pages are published, fall into the evictable pool as the most
+        # recently used, and if they survive until it is readmitted its re-prefill is skipped
+        self._publish_written(v)
         v.state = "preempted"
         self._guide_release(v)
         self.slots[v.slot] = None
@@ -662,6 +681,53 @@ class LLMEngine:
         if self.by_conv.get(v.conversation_id) is v:
             self.by_conv[v.conversation_id] = n
         self.waiting.appendleft(n)
+
+    # ------------------------------------------------------------------ prefix cache
+    # Invariant the publishing rests on: every K/V write lands on the stream all later steps run on.  Prompt rows are
+    # written by rope_kv_write of the prefill / mixed pass, decode rows by the folded QKV write in
+    # paged_attention_kernel, both on the compute stream (the TP prefill's side stream carries only the residual
+    # collectives and norms, and the main stream waits for it before the pass ends).  So a page may be published as
+    # soon as the step that writes its last position is ENQUEUED: whoever looks it up later enqueues behind it.
+    # Positions whose writes are enqueued: a prompt chunk writes [start_pos, start_pos + n), so s.prefilled prompt
+    # positions; a decode step writes the position of the token it consumes as input, so a decoding sequence has
+    # len(s.prompt) + s.decode_enqueued positions written, and the token sampled last has no K/V yet.
+    def _publish_pages(self, s: Sequence, upto: int) -> None:
+        for i in range(s.published, upto):
+            self.alloc.publish(s.blocks[i], s.hashes[i])
+        s.published = max(s.published, upto)
+
+    def _publish_prompt(self, s: Sequence) -> None:
+        """Right after the step that carries s's latest prompt chunk was enqueued: its wholly written prompt pages."""
+        if self.prefix_cache and s.blocks:
+            self._publish_pages(s, min(s.prefilled // PAGE, len(s.hashes)))
+
+    def _publish_written(self, s: Sequence) -> None:
+        """When a decoding sequence leaves (finish, abort, preemption): the full pages that generated tokens
+        completed.  The host learns those ids only from the drain, so the count is the smaller of the positions
+        written (above) and the tokens known, prompt[:orig_len] + out_ids; a late stop's wasted step wrote a position
+        past the known tokens, which is never counted.  A prompt that leaves mid-prefill publishes nothing more."""
+        if not self.prefix_cache or s.state != "decode" or not s.blocks:
+            return
+        full = s.prompt[:s.orig_len] + s.out_ids
+        pages = min(min(len(s.prompt) + s.decode_enqueued, len(full)) // PAGE, len(s.blocks))
+        if pages > len(s.hashes):
+            s.hashes = s.hashes + page_hashes(full[:pages * PAGE], s.hashes[-1] if s.hashes else b"", len(s.hashes))
+        self._publish_pages(s, pages)
+
+    def _check_write_pages(self, chunks: list, dec: list) -> None:
+        """No shared page (more than one owner, or published) may be in a step's write slots (CPU engines, or
+        DSSE_DEBUG_PREFIX_CACHE=1): a hit writes only at positions >= its cached length, on its private pages."""
+        bad = []
+        for c in chunks:
+            pages = range(c.start_pos // PAGE, (c.start_pos + len(c.tokens) - 1) // PAGE + 1)
+            bad += [(c.slot, c.block_table[i]) for i in pages if self.alloc.is_shared(c.block_table[i])]
+        for s in dec:
+            b = s.blocks[(len(s.prompt) + s.decode_enqueued) // PAGE]
+            if self.alloc.is_shared(b):
+                bad.append((s.slot, b))
+        if bad:
+            self.shared_write_violations += len(bad)
+            raise AssertionError(f"prefix cache: step {self.step_no} would write shared KV pages (slot, block): {bad}")
 
     def _grow(self):
         """Before the decode step: every sequence in it needs the page its write position falls in."""
@@ -692,20 +758,37 @@ class LLMEngine:
             if s.params.guide is not None and s.params.guide not in self._guide_idx and \
                     all(n > 0 for n in self._guide_refs):
                 return  # its pattern is not resident and every pool entry is in use: it waits, as for KV pages
-            need = blocks_needed(len(s.prompt))
+            hits = []
+            if self.prefix_cache:
+                # the resident leading pages of the prompt minus its last token: at least one token is always
+                # prefilled, so the first token is sampled by the ordinary last-chunk path.  (Hashed once; looked up
+                # on every attempt while it waits: the index changes between steps.)
+                if not s.hashes:
+                    s.hashes = page_hashes(s.prompt)
+                hits = self.alloc.lookup(s.hashes[:(len(s.prompt) - 1) // PAGE])
+            need = blocks_needed(len(s.prompt)) - len(hits)
             idle = not any(x is not None for x in self.slots)
             if need > self.alloc.num_free - (0 if idle else self.watermark):
-                if idle and need > self.alloc.num_blocks:  # can never fit: fail it rather than wait forever
+                if hits:
+                    self.alloc.free(hits)  # it waits: the references go back (the pages stay indexed)
+                if idle and need + len(hits) > self.alloc.num_blocks:  # can never fit: fail it rather than wait forever
                     self.waiting.popleft()
                     self._finish(s, self._early, reason="length")
                     continue
                 return
             self.waiting.popleft()
-            s.blocks = self.alloc.allocate(need)
+            s.blocks = hits + self.alloc.allocate(need)
             s.slot = free
             s.state = "prefill"
-            s.prefilled = 0
+            s.prefilled = PAGE * len(hits)  # its chunks start here: it writes private pages only
+            s.published = len(hits)
             s.decode_enqueued = 0
+            if self.prefix_cache:
+                if s.cached_tokens < 0:  # what the client is told: the first admission's hit, not a re-prefill's
+                    s.cached_tokens = min(s.prefilled, s.orig_len)
+                self.stats["prefix_queries"] += len(s.prompt)
+                self.stats["prefix_hit_tokens"] += s.prefilled
+                self.stats["prefix_evictions"] = self.alloc.evictions
             self.slots[s.slot] = s
             self._dirty_slots.add(s.slot)
             if s.params.penalised():
@@ -834,7 +917,8 @@ class LLMEngine:
             if budget <= 0:
                 continue
             n = min(len(s.prompt) - s.prefilled, budget)
-            if s.prefilled == 0:
+            if not s.stamped:  # (not `prefilled == 0`: a prefix-cache hit starts past 0)
+                s.stamped = True
                 s.admit_ns = time.time_ns()
             last = s.prefilled + n == len(s.prompt)
             chunks.append(PrefillSeq(slot=s.slot, tokens=s.prompt[s.prefilled:s.prefilled + n], start_pos=s.prefilled,
@@ -845,14 +929,17 @@ class LLMEngine:
                 finished.append(s)
         return chunks, finished
 
-    def _finish(self, s: Sequence, events: list, reason: str = "stop", text: str = "[DONE]"):
+    def _finish(self, s: Sequence, events: list, reason: str = "stop", text: str = "[DONE]", publish: bool = True):
         if s.state == "finished":
             return
+        if publish:
+            self._publish_written(s)  # (before its pages are freed: published ones stay indexed, evictable)
         s.state = "finished"
         self._guide_release(s)
         now = time.time_ns()
         events.append(TokenEvent(s.conversation_id, -1, s.produced + 1, True, text=text, timestamp_ns=now,
-                                 finish=reason, prompt_tokens=s.orig_len))
+                                 finish=reason, prompt_tokens=s.orig_len,
+                                 cached_tokens=max(0, s.cached_tokens) if self.prefix_cache else -1))
         if s.slot >= 0 and self.slots[s.slot] is s:
             self.slots[s.slot] = None
             self._dirty_slots.add(s.slot)
@@ -894,6 +981,8 @@ class LLMEngine:
         B = next(b for b in batch_buckets(r.max_batch) if b >= max(s.slot for s in dec) + 1) if dec else 0
         # a mixed step only when the chunks fit its captured graph (a starved prompt's big budget: separate passes)
         mixed = bool(chunks) and bool(dec) and self.mixed and self._mixed_fits(B, chunks)
+        if self.prefix_cache and self.debug_shared_writes:
+            self._check_write_pages(chunks, dec)
         if chunks:
             if not mixed:
                 done = (self.cost.record("prefill", sum(len(c.tokens) for c in chunks))
@@ -937,6 +1026,11 @@ class LLMEngine:
         elif ran:
             from .. import ops
             ops.ring_advance(r.ring_counter)
+        if self.prefix_cache:
+            # the pass that writes these chunks' K/V is enqueued (separately or inside the mixed step): the prompt
+            # pages it completed may be shared by anything admitted from now on
+            for c in chunks:
+                self._publish_prompt(self.slots[c.slot])
         for s in prefill_done:
             s.state = "decode"
             self._dirty_slots.add(s.slot)
@@ -982,6 +1076,8 @@ class LLMEngine:
                     s is p for _, _, prods, _, _ in self.inflight for _, p in prods):
                 self._finish(s, events, reason="abort")
         self.stats["steps"] += 1
+        if self.prefix_cache:
+            self.stats["prefix_evictions"] = self.alloc.evictions
         dt = time.perf_counter() - t0
         self.stats["last_step_s"] = dt
         self.stats["wait_s"] = wait
@@ -1033,7 +1129,7 @@ class LLMEngine:
         self.inflight.clear()
         for s in list(self.slots) + list(self.waiting):
             if s is not None and s.state != "finished":
-                self._finish(s, events, reason="abort", text=text)
+                self._finish(s, events, reason="abort", text=text, publish=False)  # (untrusted KV is never indexed)
         self.waiting.clear()
         return events
 

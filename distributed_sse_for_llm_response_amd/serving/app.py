@@ -60,7 +60,8 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
     tok = get_tokenizer(mcfg.vocab_size, cfg.tokenizer_path or None)
     runner.set_guide_vocab(tok.pieces(), tok.eos_id)  # guided decoding constrains the text: the pieces' bytes
     engine = LLMEngine(runner, eos_id=tok.eos_id, prefill_budget=cfg.prefill_budget, max_pause_s=cfg.max_pause_s,
-                       default_params=SamplingParams(temperature=cfg.temperature, max_tokens=cfg.max_tokens))
+                       default_params=SamplingParams(temperature=cfg.temperature, max_tokens=cfg.max_tokens),
+                       prefix_cache=cfg.enable_prefix_caching)
     return engine, tok
 
 
@@ -75,6 +76,7 @@ class EngineLoop(threading.Thread):
     halted = False
     pub_lock = threading.Lock()  # class default (a loop built without __init__); each loop sets its own
     stops = None                 # (likewise: no stop-string matching)
+    _prefix_cache = False        # (likewise: no cached_tokens on the terminal events, no prefix-cache counters)
 
     def __init__(self, runtime, engine: LLMEngine, tokenizer, cfg: ServeConfig):
         super().__init__(daemon=True, name="engine-loop")
@@ -90,6 +92,12 @@ class EngineLoop(threading.Thread):
         self._remote = hasattr(runtime, "observe")
         self._ttft, self._itl, self._host = [], [], []
         self._last_obs = 0.0
+        # prefix caching (a TP leader wraps the engine): its counters reach /metrics as deltas, the way the TTFT
+        # samples do -- straight into the in-process runtime, or with a DP worker's stats message
+        self._prefix_cache = bool(getattr(getattr(engine, "engine", engine), "prefix_cache", False))
+        self._prefix_seen = [0, 0, 0]
+        if self._prefix_cache and not self._remote:
+            rt.observe_prefix_cache(0, 0, 0)  # /metrics shows the counters from the start
         self.faults = FaultPlan.from_env()
         self.tracer = StepTracer()
         self.last_progress = time.monotonic()
@@ -185,8 +193,11 @@ class EngineLoop(threading.Thread):
                 [e.sequence for e in events], [e.done for e in events], 0,
                 [e.text for e in events], [FINISH_CODES.get(e.finish, 0) for e in events],
                 [e.prompt_tokens for e in events])
-        if any(e.logprob is not None for e in events):
-            self.rt.publish_tokens(*args, [self.logprobs_entry(e) for e in events])
+        lps = [self.logprobs_entry(e) for e in events] if any(e.logprob is not None for e in events) else []
+        if self._prefix_cache:  # cached_tokens rides beside prompt_tokens on the terminal events
+            self.rt.publish_tokens(*args, lps, [getattr(e, "cached_tokens", -1) for e in events])
+        elif lps:
+            self.rt.publish_tokens(*args, lps)
         else:
             self.rt.publish_tokens(*args)
 
@@ -233,6 +244,10 @@ class EngineLoop(threading.Thread):
         if not self._remote:
             self._rt.engine_observe(e.stats["last_step_s"], running, free, host)
             self._rt.set_active_chats(running + len(e.waiting))
+            if self._prefix_cache:
+                d = self._prefix_delta()
+                if any(d):
+                    self._rt.observe_prefix_cache(*d)
             return
         if host >= 0:
             self._host.append(host)
@@ -244,7 +259,19 @@ class EngineLoop(threading.Thread):
         self._ttft.clear()
         self._itl.clear()
         self._host.clear()
-        self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs)
+        if self._prefix_cache:
+            self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs,
+                            self._prefix_delta())
+        else:
+            self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs)
+
+    def _prefix_delta(self) -> list:
+        """[queries, hits (prompt tokens), evictions (pages)] of the engine's prefix cache since the last call."""
+        st = self.engine.stats
+        now = [st.get("prefix_queries", 0), st.get("prefix_hit_tokens", 0), st.get("prefix_evictions", 0)]
+        d = [float(a - b) for a, b in zip(now, self._prefix_seen)]
+        self._prefix_seen = now
+        return d
 
     def _shutdown(self) -> bool:
         f = getattr(self.rt, "shutdown_requested", None)

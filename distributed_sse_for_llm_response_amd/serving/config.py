@@ -9,7 +9,8 @@ Topology keys (new): UPSTREAM_URL (edge: relay conversations from the origin), U
 Flow control (new): FLOW_HIGH_WATER (bytes queued for every subscriber of a conversation before its decode
   pauses; 0 = off), MAX_PAUSE_S (a paused stream resumes after this long regardless).
 Engine keys (new): TP, DP, DP_PREFIX, DP_WORKER_TIMEOUT_MS, MAX_MODEL_LEN, MAX_BATCH, KV_BLOCK (fixed 32), GPU_MEMORY_UTILIZATION,
-  SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH.
+  SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH, ENABLE_PREFIX_CACHING (default 0),
+  DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured).
 """
 from __future__ import annotations
 
@@ -69,6 +70,11 @@ class ServeConfig:
     stub_token_delay_ms: int = 50
     dp_prefix: str = ""          # shared-memory ring name prefix of a DP group (default from MASTER_PORT)
     dp_worker_timeout_ms: int = 10000
+    # automatic prefix caching (engine/kv_cache.py): off by default; passed to every engine replica
+    enable_prefix_caching: bool = False
+    # DP router: a chat's affine replica wins while its outstanding count is at most the least one plus this slack
+    # (only with prefix caching on; the default is a guess nobody has measured)
+    dp_prefix_affinity_slack: int = 4
 
     @classmethod
     def from_env(cls) -> "ServeConfig":
@@ -111,11 +117,16 @@ class ServeConfig:
         c.stub_token_delay_ms = _env("STUB_TOKEN_DELAY_MS", c.stub_token_delay_ms, int)
         c.dp_prefix = _env("DP_PREFIX", c.dp_prefix)
         c.dp_worker_timeout_ms = _env("DP_WORKER_TIMEOUT_MS", c.dp_worker_timeout_ms, int)
+        c.enable_prefix_caching = _env("ENABLE_PREFIX_CACHING", c.enable_prefix_caching, bool)
+        c.dp_prefix_affinity_slack = _env("DP_PREFIX_AFFINITY_SLACK", c.dp_prefix_affinity_slack, int)
         return c
 
     @classmethod
     def add_args(cls, ap: argparse.ArgumentParser):
         for f in fields(cls):
+            if isinstance(f.default, bool):  # a switch: --enable-prefix-caching
+                ap.add_argument("--" + f.name.replace("_", "-"), action="store_const", const=True, default=None)
+                continue
             ap.add_argument("--" + f.name.replace("_", "-"), type=type(f.default) if f.default is not None else str,
                             default=None)
 

@@ -43,7 +43,9 @@ def start_router(cfg: ServeConfig, workers: int):
     rt = mod.Runtime(rd)
     mcfg = TINY if (cfg.engine == "cpu" and cfg.model.startswith("mistral-7b")) else get_config(cfg.model)
     rt.set_vocab(get_tokenizer(mcfg.vocab_size, cfg.tokenizer_path or None).pieces())
-    rt.start_dp_router(dp_prefix(cfg), workers, 8, cfg.dp_worker_timeout_ms)
+    # prefix caching on: the turns of one conversation prefer the replica that holds its KV pages (dp.h)
+    rt.start_dp_router(dp_prefix(cfg), workers, 8, cfg.dp_worker_timeout_ms,
+                       cfg.dp_prefix_affinity_slack if cfg.enable_prefix_caching else -1)
     rt.start()
     return rt
 

@@ -21,6 +21,74 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def cached_prefix_main(args):
+    """TTFT of a prompt whose first N tokens are resident in the prefix cache, against the same engine without it.
+
+    One runner, two engines over it, used one after the other: cache off and cache on.  Per iteration, with fresh
+    random tokens: prompt 1 (`--prompt-len`) runs to its first token on both engines (a miss on the cache-on one: its
+    TTFT is the cache's bookkeeping on top of a full prefill); prompt 2 = prompt 1's first N tokens + new ones runs
+    on both: a full prefill with the cache off, N // 32 * 32 tokens skipped with it on.  TTFT = add_request to the
+    first token event on the host (engine steps included, so it is the engine's TTFT, not the bare prefill call's)."""
+    import numpy as np
+    import torch
+
+    from distributed_sse_for_llm_response_amd.engine.engine import LLMEngine, SamplingParams
+    from distributed_sse_for_llm_response_amd.engine.kv_cache import PAGE, blocks_needed
+    from distributed_sse_for_llm_response_amd.engine.model_runner import ModelRunner
+    from distributed_sse_for_llm_response_amd.engine.weights import random_engine_weights
+    from distributed_sse_for_llm_response_amd.models.mistral import get_config
+
+    n, keep = args.prompt_len, args.cached_prefix
+    if not 0 <= keep < n:
+        raise SystemExit("--cached-prefix must be in [0, --prompt-len)")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    cfg = get_config(args.model)
+    w = random_engine_weights(cfg, device=device, seed=7)
+    max_len = n + 4 * PAGE
+    r = ModelRunner(w, num_blocks=4 * blocks_needed(max_len) + 4, max_batch=2, max_model_len=max_len, device=device,
+                    max_prefill_tokens=max(args.chunk, 8192))
+    r.capture()
+    engines = {on: LLMEngine(r, eos_id=-1, prefill_budget=r.max_prefill_tokens, prefix_cache=on) for on in (False, True)}
+    gen = torch.Generator().manual_seed(5)
+    ids = iter(range(1 << 30))
+
+    def ttft(e, prompt):
+        torch.cuda.synchronize()
+        e.ring_head = int(r.ring_counter.item())  # (the other engine advanced the runner's token ring meanwhile)
+        t0 = time.perf_counter()
+        e.add_request(f"r{next(ids)}", prompt, SamplingParams(temperature=0.0, max_tokens=2))
+        dt, cached = None, -1
+        while e.has_work():
+            for ev in e.step():
+                if dt is None and not ev.done:
+                    dt = time.perf_counter() - t0
+                if ev.done:
+                    cached = ev.cached_tokens
+        return dt, cached
+
+    rows = {"off_first": [], "off_second": [], "on_miss": [], "on_hit": []}
+    cached = 0
+    for it in range(args.iters + 1):  # the first iteration warms up (allocator, first launches) and is dropped
+        p1 = torch.randint(3, cfg.vocab_size, (n,), generator=gen).tolist()
+        p2 = p1[:keep] + torch.randint(3, cfg.vocab_size, (n - keep,), generator=gen).tolist()
+        a = ttft(engines[False], p1)[0]
+        b = ttft(engines[False], p2)[0]
+        c = ttft(engines[True], p1)[0]
+        d, cached = ttft(engines[True], p2)
+        if it:
+            for k, v in zip(rows, (a, b, c, d)):
+                rows[k].append(v)
+    med = {k: round(1000 * float(np.median(v)), 3) for k, v in rows.items()}
+    print(json.dumps({
+        "metric": "TTFT with a cached prefix (engine add_request -> first token on the host)", "model": cfg.name,
+        "prompt_len": n, "cached_prefix": keep, "cached_tokens": cached, "iters": args.iters,
+        "ttft_ms_cache_off": med["off_second"], "ttft_ms_cache_on_hit": med["on_hit"],
+        "ttft_ms_cache_off_first_prompt": med["off_first"], "ttft_ms_cache_on_miss": med["on_miss"],
+        "all_ms": {k: [round(1000 * x, 3) for x in v] for k, v in rows.items()},
+        "dtype": "bf16", "data": "synthetic prompts, random-init weights"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="mistral-7b-v0.3")
@@ -32,7 +100,13 @@ def main():
     ap.add_argument("--profile-marker", action="store_true",
                     help="launch one bitwise_not kernel after the warm-up iteration: tools/trace_sum.py --after-kernel "
                          "bitwise_not then keeps only the timed iterations of a rocprofv3 kernel trace")
+    ap.add_argument("--cached-prefix", type=int, default=None, metavar="N",
+                    help="prefix caching: prefill one prompt, then time a second one that shares its first N tokens, "
+                         "through the engine with the cache on, and the same second prompt with the cache off "
+                         "(one GPU; both TTFTs in one JSON line)")
     args = ap.parse_args()
+    if args.cached_prefix is not None:
+        return cached_prefix_main(args)
 
     import numpy as np
     import torch
