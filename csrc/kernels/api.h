@@ -84,6 +84,12 @@ struct AttnParams {
   // head) to finish instead of attn_combine_kernel (round 6): [num_work * hkv] arrival tickets, zero between
   // launches (the last arriver resets its ticket); null = the combine kernel
   int* comb_cnt;
+  // FP8 (e4m3) KV cache: k_cache / v_cache (k_out / v_out) point at bytes, same shapes and element order.  Stored
+  // value = x / scale.  The host folds k_scale into scale_log2; v_scale multiplies the final 1 / l normalisation;
+  // k_inv = 1 / k_scale and v_inv = 1 / v_scale quantise the folded write (mode 3).  All four are read by the f8
+  // instantiations only.  The flash prefill kernels (attention_prefill.hip) have no f8 form and refuse kv_f8.
+  int kv_f8;
+  float v_scale, k_inv, v_inv;
 };
 
 struct SampleParams {
@@ -229,6 +235,13 @@ hipError_t dsse_rmsnorm(int mode, int M, float* resid, int H, const void* delta,
 hipError_t dsse_rope_kv_write(int T, const void* qkv, int hq, int hkv, const int* positions,
                               const int* slots, const float2* rope, void* q_out, void* k_cache,
                               void* v_cache, int num_slots, int rope_len, hipStream_t st);
+// FP8 (e4m3) cache writers: k_inv = 1 / k_scale, v_inv = 1 / v_scale; y = the QKV projection's fp32 output
+hipError_t dsse_rope_kv_write_f8(int T, const void* qkv, int hq, int hkv, const int* positions, const int* slots,
+                                 const float2* rope, void* q_out, void* k_cache, void* v_cache, int num_slots,
+                                 int rope_len, float k_inv, float v_inv, hipStream_t st);
+hipError_t dsse_qkv_rope_f8(int M, const float* y, int hq, int hkv, const int* positions, const int* slots,
+                            const float2* rope, void* q_out, void* k_cache, void* v_cache, int num_slots,
+                            int rope_len, float k_inv, float v_inv, hipStream_t st);
 hipError_t dsse_silu_mul(int T, int F, const void* gu, void* h, hipStream_t st);
 hipError_t dsse_decode_prep(int B, const int* active, const int* positions, const int* block_tables,
                             int max_blocks, int num_blocks, int* slots, int* ctx_len, int* q_len, hipStream_t st);

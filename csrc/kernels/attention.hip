@@ -18,6 +18,7 @@
 // by attn_combine_kernel.  Online softmax in base 2 with a finite initial max, so fully masked
 // columns stay finite and produce zeros.
 #include <cstdlib>
+#include <type_traits>
 
 #include "api.h"
 #include "gemm_epilogue.h"
@@ -47,10 +48,32 @@ DEV int part_keys(const AttnParams& p, int kmax) {
   return max(kPage, (per + kPage - 1) / kPage * kPage);
 }
 
-template <int QW, int KWV, int PD = 1, int FQG = 0>
+// KV = bf16, or f8: an FP8 (e4m3) cache.  A key row is then 128 bytes and a V page row 32 bytes; the fragments are
+// widened to bf16 in registers (exact) and feed the same MFMAs.  The host folds k_scale into p.scale_log2 and passes
+// v_scale for the final normalisation, so the key loop carries no extra multiply.  K fragment order under f8: a lane
+// takes one 16-byte run d = 64 s2 + 16 g + [0, 16) covering k-steps 2 s2 and 2 s2 + 1 (each K load instruction still
+// reads 64 contiguous bytes of 16 rows; 8-byte loads at 32 s + 8 g would touch 16 rows x 32 B), and Q's fragments are
+// loaded in the matching head-dim order -- Q and K only have to agree inside the k-step set.
+template <int QW, int KWV, int PD = 1, int FQG = 0, typename KV = bf16>
 __global__ void __launch_bounds__(64 * QW * KWV, QW * KWV == 1 ? (PD > 1 ? 2 : 4) : 1)
 paged_attention_kernel(AttnParams p) {
   constexpr bool FQ = FQG > 0;  // QKV epilogue folded in, GQA group FQG (= p.group)
+  constexpr bool F8 = sizeof(KV) == 1;
+  // head dim of element 0 of lane group g's fragment in k-step s (8 consecutive dims)
+  auto dofs = [](int s, int g) { return F8 ? 64 * (s >> 1) + 16 * g + 8 * (s & 1) : 32 * s + 8 * g; };
+  // Fragments as loaded: under f8 the raw bytes stay in registers (half the registers of the bf16 form, and the
+  // widening VALU work sits at the MFMAs, not behind the loads of a page still in flight)
+  using KFrag = std::conditional_t<F8, u32x4, bf16x8>;  // f8: one 16-byte run = k-steps 2 s2 and 2 s2 + 1
+  using VFrag = std::conditional_t<F8, u32x2, bf16x8>;
+  constexpr int NKF = F8 ? 2 : 4;
+  auto kfrag = [](const KFrag (&k)[NKF], int s) -> bf16x8 {
+    if constexpr (F8) return widen_f8x8(make_uint2(k[s >> 1][2 * (s & 1)], k[s >> 1][2 * (s & 1) + 1]));
+    else return k[s];
+  };
+  auto vfrag = [](const VFrag& v) -> bf16x8 {
+    if constexpr (F8) return widen_f8x8(make_uint2(v[0], v[1]));
+    else return v;
+  };
   static_assert(PD == 1 || PD == 2, "1 or 2 pages in flight");
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
@@ -92,27 +115,48 @@ paged_attention_kernel(AttnParams p) {
   // (QW > 1) share the lines through L1
   constexpr bool NT = ATTN_DECODE_NT && QW == 1;
   auto ldkv = [&](const bf16* a) { return NT ? ld_nt_bf16x8(a) : ld_bf16x8(a); };
-  auto load_k = [&](int page, bf16x8 (&k0)[4], bf16x8 (&k1)[4]) {
-    const bf16* kp = p.k_cache + ((size_t)page * p.hkv + h) * kPage * kD;
-    // K rows for keys kb + r and kb + 16 + r; k-step s of the 4 lane groups = 64 contiguous bytes of a row.
+  auto load_k = [&](int page, KFrag (&k0)[NKF], KFrag (&k1)[NKF]) {
+    if constexpr (F8) {
+      const f8* kp = reinterpret_cast<const f8*>(p.k_cache) + ((size_t)page * p.hkv + h) * kPage * kD;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      k0[s] = ldkv(kp + (size_t)r * kD + 32 * s + 8 * g);
-      k1[s] = ldkv(kp + (size_t)(16 + r) * kD + 32 * s + 8 * g);
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const u32x4* a0 = reinterpret_cast<const u32x4*>(kp + (size_t)r * kD + 64 * s2 + 16 * g);
+        const u32x4* a1 = reinterpret_cast<const u32x4*>(kp + (size_t)(16 + r) * kD + 64 * s2 + 16 * g);
+        k0[s2] = NT ? __builtin_nontemporal_load(a0) : *a0;
+        k1[s2] = NT ? __builtin_nontemporal_load(a1) : *a1;
+      }
+    } else {
+      const bf16* kp = p.k_cache + ((size_t)page * p.hkv + h) * kPage * kD;
+      // K rows for keys kb + r and kb + 16 + r; k-step s of the 4 lane groups = 64 contiguous bytes of a row.
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        k0[s] = ldkv(kp + (size_t)r * kD + 32 * s + 8 * g);
+        k1[s] = ldkv(kp + (size_t)(16 + r) * kD + 32 * s + 8 * g);
+      }
     }
   };
-  auto load_v = [&](int page, bf16x8 (&vf)[8]) {
-    const bf16* vp = p.v_cache + ((size_t)page * p.hkv + h) * kD * kPage;
+  auto load_v = [&](int page, VFrag (&vf)[8]) {
+    if constexpr (F8) {
+      // 8 bytes per lane: the 16 rows of an instruction are one contiguous 512-byte run
+      const f8* vp = reinterpret_cast<const f8*>(p.v_cache) + ((size_t)page * p.hkv + h) * kD * kPage;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) vf[dt] = ldkv(vp + (size_t)(16 * dt + r) * kPage + 8 * g);
+      for (int dt = 0; dt < 8; ++dt) {
+        const u32x2* a = reinterpret_cast<const u32x2*>(vp + (size_t)(16 * dt + r) * kPage + 8 * g);
+        vf[dt] = NT ? __builtin_nontemporal_load(a) : *a;
+      }
+    } else {
+      const bf16* vp = p.v_cache + ((size_t)page * p.hkv + h) * kD * kPage;
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt) vf[dt] = ldkv(vp + (size_t)(16 * dt + r) * kPage + 8 * g);
+    }
   };
-  auto load_page = [&](int page, bf16x8 (&k0)[4], bf16x8 (&k1)[4], bf16x8 (&vf)[8]) {
+  auto load_page = [&](int page, KFrag (&k0)[NKF], KFrag (&k1)[NKF], VFrag (&vf)[8]) {
     load_k(page, k0, k1);
     load_v(page, vf);
   };
   constexpr int kStep = 32 * KWV;
   const int kb0 = kbeg + 32 * kw;  // this wave's first page: keys kb0 + i * kStep
-  bf16x8 rk0[PD][4], rk1[PD][4];   // K rows of the pages in flight (FQ: slot 0 loaded under the slab sums)
+  KFrag rk0[PD][NKF], rk1[PD][NKF];   // K rows of the pages in flight (FQ: slot 0 loaded under the slab sums)
   // Q fragments (B operand): lane (r, g) holds Q[col r][d = 32s + 8g + j] in k-step s — the same head-dim
   // order as the K fragments, so each K load instruction reads 64 contiguous bytes of 16 key rows.
   bf16x8 qf[4];
@@ -189,17 +233,28 @@ paged_attention_kernel(AttnParams p) {
       fq[u * kD + 64 + d] = f2bf(qa[u][1] * c.x + qa[u][0] * c.y);
     }
     if (owner) {
-      fq[kMaxG * kD + d] = f2bf(ka[0] * c.x - ka[1] * c.y);
-      fq[kMaxG * kD + 64 + d] = f2bf(ka[1] * c.x + ka[0] * c.y);
-      fq[(kMaxG + 1) * kD + d] = f2bf(va[0]);
-      fq[(kMaxG + 1) * kD + 64 + d] = f2bf(va[1]);
+      if constexpr (F8) {
+        // The newest key enters attention as its cache value: quantised from the fp32 value, then dequantised (the
+        // stored e4m3 value, exact in bf16; the scales are folded into scale_log2 / the final normalisation) -- this
+        // step's output is what a later launch reading the key from the cache would compute.
+        auto qd = [](float x, float inv) { return f2bf(f8_to_f(quant_f8(x, inv))); };
+        fq[kMaxG * kD + d] = qd(ka[0] * c.x - ka[1] * c.y, p.k_inv);
+        fq[kMaxG * kD + 64 + d] = qd(ka[1] * c.x + ka[0] * c.y, p.k_inv);
+        fq[(kMaxG + 1) * kD + d] = qd(va[0], p.v_inv);
+        fq[(kMaxG + 1) * kD + 64 + d] = qd(va[1], p.v_inv);
+      } else {
+        fq[kMaxG * kD + d] = f2bf(ka[0] * c.x - ka[1] * c.y);
+        fq[kMaxG * kD + 64 + d] = f2bf(ka[1] * c.x + ka[0] * c.y);
+        fq[(kMaxG + 1) * kD + d] = f2bf(va[0]);
+        fq[(kMaxG + 1) * kD + 64 + d] = f2bf(va[1]);
+      }
     }
     // LDS rows written and read by this wave only: in-order LDS, no barrier; keep the compiler from hoisting
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int s = 0; s < 4; ++s)
-      qf[s] = col_valid ? *reinterpret_cast<const bf16x8*>(&fq[(r % G) * kD + 32 * s + 8 * g]) : zero_bf16x8();
+      qf[s] = col_valid ? *reinterpret_cast<const bf16x8*>(&fq[(r % G) * kD + dofs(s, g)]) : zero_bf16x8();
     if (owner) {
       kb_new = kn_page;
       key_limit = col_limit - 1;  // decode: the newest key is the last visible one
@@ -207,7 +262,7 @@ paged_attention_kernel(AttnParams p) {
       float dot = 0.f;  // q · k over this lane's 32 head dims, then over the 4 lane groups
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        kn[q] = *reinterpret_cast<const bf16x8*>(&fq[kMaxG * kD + 32 * q + 8 * g]);
+        kn[q] = *reinterpret_cast<const bf16x8*>(&fq[kMaxG * kD + dofs(q, g)]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) dot += bf2f(qf[q][e]) * bf2f(kn[q][e]);
       }
@@ -216,20 +271,42 @@ paged_attention_kernel(AttnParams p) {
       sc_new = col_valid ? dot * p.scale_log2 : -INFINITY;
       // cache copies for later steps
       const int sidx = DSSE_IDX(sl, p.num_slots, 0), blk = sidx / kPage, off = sidx % kPage;
-      if (r == (off & 15)) {
-        bf16* kdst = p.k_out + (((size_t)blk * p.hkv + h) * kPage + off) * kD + 8 * g;
+      if constexpr (F8) {
+        if (r == (off & 15)) {
+          f8* kdst = reinterpret_cast<f8*>(p.k_out) + (((size_t)blk * p.hkv + h) * kPage + off) * kD;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) *reinterpret_cast<bf16x8*>(kdst + 32 * q) = kn[q];
+          for (int q = 0; q < 4; ++q) {
+            float kv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kv[e] = bf2f(kn[q][e]);  // already e4m3 values: the convert is exact
+            *reinterpret_cast<uint2*>(kdst + dofs(q, g)) = quant_f8x8(kv, 1.f);
+          }
+        }
+        f8* vdst = reinterpret_cast<f8*>(p.v_out) + ((size_t)blk * p.hkv + h) * kD * kPage + vperm_tok(off);
+        store_kv(vdst + (size_t)d * kPage, va[0], p.v_inv);
+        store_kv(vdst + (size_t)(64 + d) * kPage, va[1], p.v_inv);
+      } else {
+        if (r == (off & 15)) {
+          bf16* kdst = p.k_out + (((size_t)blk * p.hkv + h) * kPage + off) * kD + 8 * g;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) *reinterpret_cast<bf16x8*>(kdst + 32 * q) = kn[q];
+        }
+        bf16* vdst = p.v_out + ((size_t)blk * p.hkv + h) * kD * kPage + vperm_tok(off);
+        vdst[(size_t)d * kPage] = f2bf(va[0]);
+        vdst[(size_t)(64 + d) * kPage] = f2bf(va[1]);
       }
-      bf16* vdst = p.v_out + ((size_t)blk * p.hkv + h) * kD * kPage + vperm_tok(off);
-      vdst[(size_t)d * kPage] = f2bf(va[0]);
-      vdst[(size_t)(64 + d) * kPage] = f2bf(va[1]);
     }
   } else {
     const int qrow = p.q_start[b] + (col_valid ? qi : 0);
-    const bf16* qp = p.q + ((size_t)qrow * p.hq + h * G + (r % G)) * kD + 8 * g;
+    if constexpr (F8) {
+      const bf16* qp = p.q + ((size_t)qrow * p.hq + h * G + (r % G)) * kD;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = col_valid ? ld_bf16x8(qp + 32 * s) : zero_bf16x8();
+      for (int s = 0; s < 4; ++s) qf[s] = col_valid ? ld_bf16x8(qp + dofs(s, g)) : zero_bf16x8();
+    } else {
+      const bf16* qp = p.q + ((size_t)qrow * p.hq + h * G + (r % G)) * kD + 8 * g;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qf[s] = col_valid ? ld_bf16x8(qp + 32 * s) : zero_bf16x8();
+    }
   }
 
   float m_run = -1e30f, l_run = 0.f;
@@ -250,12 +327,12 @@ paged_attention_kernel(AttnParams p) {
     }
   }
 
-  auto compute_page = [&](int kb, const bf16x8 (&k0)[4], const bf16x8 (&k1)[4], const bf16x8 (&vf)[8]) {
+  auto compute_page = [&](int kb, const KFrag (&k0)[NKF], const KFrag (&k1)[NKF], const VFrag (&vf)[8]) {
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      s0 = mfma16x16x32(k0[s], qf[s], s0);
-      s1 = mfma16x16x32(k1[s], qf[s], s1);
+      s0 = mfma16x16x32(kfrag(k0, s), qf[s], s0);
+      s1 = mfma16x16x32(kfrag(k1, s), qf[s], s1);
     }
     // element i: key kb + 4g + i (s0) / kb + 16 + 4g + i (s1), column r
     float tmax = -INFINITY;
@@ -284,7 +361,7 @@ paged_attention_kernel(AttnParams p) {
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) {
       f32x4 acc = o[dt] * alpha;
-      o[dt] = mfma16x16x32(vf[dt], pf, acc);
+      o[dt] = mfma16x16x32(vfrag(vf[dt]), pf, acc);
     }
   };
   int kb = kb0;
@@ -293,7 +370,7 @@ paged_attention_kernel(AttnParams p) {
     int page = kb < kend ? page_of(kb) : 0;
     if constexpr (FQ) {
       if (kb < kend) {  // the first page's K has been in flight since the slab sums
-        bf16x8 vf[8];
+        VFrag vf[8];
         load_v(page, vf);
         page = page_of(min(kb + kStep, kend - 1));
         compute_page(kb, rk0[0], rk1[0], vf);
@@ -301,7 +378,8 @@ paged_attention_kernel(AttnParams p) {
       }
     }
     for (; kb < kend; kb += kStep) {
-      bf16x8 k0[4], k1[4], vf[8];
+      KFrag k0[NKF], k1[NKF];
+      VFrag vf[8];
       load_page(page, k0, k1, vf);
       page = page_of(min(kb + kStep, kend - 1));
       compute_page(kb, k0, k1, vf);
@@ -310,7 +388,7 @@ paged_attention_kernel(AttnParams p) {
     // Register ring of PD pages: page i + PD - 1 is issued before page i is computed.  Look-ahead loads past the
     // wave's last page re-read that page (an L2 hit) instead of branching around them -- hipcc waits vmcnt(0)
     // at such a join, which would serialise the ring.  Page indices are fetched one issue ahead.
-    bf16x8 rv[PD][8];
+    VFrag rv[PD][8];
     const int n = (kend - kb + kStep - 1) / kStep;  // pages of this wave
     auto pg = [&](int i) { return page_of(kb0 + min(i, n - 1) * kStep); };
     if constexpr (FQ) load_v(pg(0), rv[0]);
@@ -372,7 +450,8 @@ paged_attention_kernel(AttnParams p) {
   // element (dt, i) of lane (r, g): d = 16dt + 4g + i, column r
   if (p.nparts == 1) {
     if (!col_valid) return;
-    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    if constexpr (F8) inv *= p.v_scale;
     bf16* op = p.out + ((size_t)(p.q_start[b] + qi) * p.hq + h * G + (r % G)) * kD;
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt)
@@ -419,7 +498,8 @@ paged_attention_kernel(AttnParams p) {
           for (int dt = 0; dt < 8; ++dt) acc[dt] += *reinterpret_cast<const f32x4*>(pz_o + 16 * dt) * sc;
         }
         if (!col_valid) return;
-        const float inv = ll > 0.f ? 1.f / ll : 0.f;
+        float inv = ll > 0.f ? 1.f / ll : 0.f;
+        if constexpr (F8) inv *= p.v_scale;
         bf16* op = p.out + ((size_t)(p.q_start[b] + qi) * p.hq + h * G + (r % G)) * kD;
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt)
@@ -432,7 +512,7 @@ paged_attention_kernel(AttnParams p) {
 
 // Merge flash-decoding partitions: grid (num_work, hkv, QW), block 256 = (16 columns × 16 lanes),
 // each thread owns 8 head dims of one column.
-template <int QW>
+template <int QW, bool F8 = false>
 __global__ void __launch_bounds__(256) attn_combine_kernel(AttnParams p) {
   const int item = blockIdx.x, h = blockIdx.y, qw = blockIdx.z;
   const int col = threadIdx.x >> 4, sub = threadIdx.x & 15;
@@ -462,7 +542,8 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(AttnParams p) {
     acc[0] += a.x * sc; acc[1] += a.y * sc; acc[2] += a.z * sc; acc[3] += a.w * sc;
     acc[4] += c.x * sc; acc[5] += c.y * sc; acc[6] += c.z * sc; acc[7] += c.w * sc;
   }
-  const float inv = ll > 0.f ? 1.f / ll : 0.f;
+  float inv = ll > 0.f ? 1.f / ll : 0.f;
+  if constexpr (F8) inv *= p.v_scale;  // FP8 cache: the partials hold stored (unscaled) values
   bf16x8 ov;
 #pragma unroll
   for (int j = 0; j < 8; ++j) ov[j] = f2bf(acc[j] * inv);
@@ -470,25 +551,22 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(AttnParams p) {
   *reinterpret_cast<bf16x8*>(op) = ov;
 }
 
-template <int G>
+template <int G, typename KV>
 hipError_t launch_folded(int kwv, int pd, dim3 grid, const AttnParams& p, hipStream_t st) {
-  if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, G>), grid, dim3(512), 0, st, p);
-  else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, G>), grid, dim3(64), 0, st, p);
-  else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, G>), grid, dim3(64), 0, st, p);
-  else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, G>), grid, dim3(128), 0, st, p);
-  else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, G>), grid, dim3(128), 0, st, p);
-  else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, G>), grid, dim3(256), 0, st, p);
+  if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, G, KV>), grid, dim3(512), 0, st, p);
+  else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, G, KV>), grid, dim3(64), 0, st, p);
+  else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, G, KV>), grid, dim3(64), 0, st, p);
+  else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, G, KV>), grid, dim3(128), 0, st, p);
+  else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, G, KV>), grid, dim3(128), 0, st, p);
+  else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, G, KV>), grid, dim3(256), 0, st, p);
   return hipGetLastError();
 }
 
-}  // namespace dsse
-
 // mode 0 = decode (QW = 1, KWV = 4), mode 1 = prefill (QW = 4, KWV = 1), mode 3 = decode reading q from the
-// QKV GEMM's split-K slabs and writing the step's K / V (AttnParams::qkv_part).
-extern "C" hipError_t dsse_paged_attention(int mode, int num_work, const dsse::AttnParams* p,
-                                           hipStream_t st) {
-  using namespace dsse;
-  if (num_work <= 0) return hipSuccess;
+// QKV GEMM's split-K slabs and writing the step's K / V (AttnParams::qkv_part).  KV = the cache element type.
+template <typename KV>
+hipError_t launch_paged(int mode, int num_work, const AttnParams* p, hipStream_t st) {
+  constexpr bool F8 = sizeof(KV) == 1;
   if (mode == 3) {
     // decode with the QKV epilogue folded in; GQA group 1, 2 or 4.  Every key-split wave sums its q slabs, so
     // fewer waves per workgroup than mode 0 pay off: 2 from 512 workgroups (64 streams: 4.58 vs 4.60 ms/step,
@@ -503,13 +581,13 @@ extern "C" hipError_t dsse_paged_attention(int mode, int num_work, const dsse::A
     const int kwv = p->kwv ? p->kwv : (nwg >= 2048 ? 1 : (nwg >= 512 ? 2 : 4));
     const int pd = p->pd ? p->pd : 1;
     hipError_t e;
-    if (p->group == 1) e = launch_folded<1>(kwv, pd, grid, *p, st);
-    else if (p->group == 2) e = launch_folded<2>(kwv, pd, grid, *p, st);
-    else if (p->group == 4) e = launch_folded<4>(kwv, pd, grid, *p, st);
+    if (p->group == 1) e = launch_folded<1, KV>(kwv, pd, grid, *p, st);
+    else if (p->group == 2) e = launch_folded<2, KV>(kwv, pd, grid, *p, st);
+    else if (p->group == 4) e = launch_folded<4, KV>(kwv, pd, grid, *p, st);
     else return hipErrorInvalidValue;
     if (e != hipSuccess) return e;
     if (p->nparts > 1 && !p->comb_cnt)
-      hipLaunchKernelGGL((attn_combine_kernel<1>), dim3(num_work, p->hkv, 1), dim3(256), 0, st, *p);
+      hipLaunchKernelGGL((attn_combine_kernel<1, F8>), dim3(num_work, p->hkv, 1), dim3(256), 0, st, *p);
   } else if (mode == 0) {
     // decode: p->kwv (attn_kwv in DSSE_KERNEL_CFG, read by the bindings) = waves per workgroup splitting the keys (1/2/4/8).
     // Measured (profiles/attention_decode_r1.md): 4 key-split waves are best up to ~1k workgroups (64 streams x
@@ -518,21 +596,32 @@ extern "C" hipError_t dsse_paged_attention(int mode, int num_work, const dsse::A
     const dim3 grid(num_work, p->hkv, p->nparts);
     const int kwv = p->kwv ? p->kwv : (grid.x * grid.y * grid.z >= 2048 ? 1 : 4);
     const int pd = p->pd == 2 && kwv <= 2 ? 2 : 1;  // attn_pd=2 (DSSE_KERNEL_CFG): 2-page register ring (1 / 2 waves)
-    if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1>), grid, dim3(512), 0, st, *p);
-    else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2>), grid, dim3(64), 0, st, *p);
-    else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2>), grid, dim3(128), 0, st, *p);
-    else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1>), grid, dim3(64), 0, st, *p);
-    else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1>), grid, dim3(128), 0, st, *p);
-    else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1>), grid, dim3(256), 0, st, *p);
+    if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, 0, KV>), grid, dim3(512), 0, st, *p);
+    else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, 0, KV>), grid, dim3(64), 0, st, *p);
+    else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, 0, KV>), grid, dim3(128), 0, st, *p);
+    else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, 0, KV>), grid, dim3(64), 0, st, *p);
+    else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, 0, KV>), grid, dim3(128), 0, st, *p);
+    else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, 0, KV>), grid, dim3(256), 0, st, *p);
     if (p->nparts > 1 && !p->comb_cnt)
-      hipLaunchKernelGGL((attn_combine_kernel<1>), dim3(num_work, p->hkv, 1), dim3(256), 0, st, *p);
+      hipLaunchKernelGGL((attn_combine_kernel<1, F8>), dim3(num_work, p->hkv, 1), dim3(256), 0, st, *p);
   } else {
-    hipLaunchKernelGGL((paged_attention_kernel<4, 1>), dim3(num_work, p->hkv, p->nparts), dim3(256),
+    hipLaunchKernelGGL((paged_attention_kernel<4, 1, 1, 0, KV>), dim3(num_work, p->hkv, p->nparts), dim3(256),
                        0, st, *p);
     if (p->nparts > 1)
-      hipLaunchKernelGGL((attn_combine_kernel<4>), dim3(num_work, p->hkv, 4), dim3(256), 0, st, *p);
+      hipLaunchKernelGGL((attn_combine_kernel<4, F8>), dim3(num_work, p->hkv, 4), dim3(256), 0, st, *p);
   }
   return hipGetLastError();
+}
+
+}  // namespace dsse
+
+// p->kv_f8: the caches hold FP8 (e4m3) bytes (the bindings set it from the cache tensors' dtype).
+extern "C" hipError_t dsse_paged_attention(int mode, int num_work, const dsse::AttnParams* p,
+                                           hipStream_t st) {
+  using namespace dsse;
+  if (num_work <= 0) return hipSuccess;
+  if (mode != 0 && mode != 1 && mode != 3) return hipErrorInvalidValue;
+  return p->kv_f8 ? launch_paged<f8>(mode, num_work, p, st) : launch_paged<bf16>(mode, num_work, p, st);
 }
 
 DSSE_CHECK_READER(dsse_check_attention)

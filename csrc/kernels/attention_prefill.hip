@@ -480,6 +480,7 @@ hipError_t launch_stamped(int num_work, const dsse::AttnParams* p, hipStream_t s
 // at 2048; profiles/r6/flash_tp8_r6.log) -- every split stages the same K / V once more per workgroup, and the LDS
 // fill, not the idle CUs, sets the time.
 extern "C" hipError_t dsse_flash_prefill(int num_work, const dsse::AttnParams* p, hipStream_t st) {
+  if (p->kv_f8) return hipErrorInvalidValue;  // no f8 form: the cache bytes would be read as bf16
   if (num_work <= 0) return hipSuccess;
   static const char* stamps = getenv("DSSE_FLASH_STAMPS");
   if (stamps != nullptr && stamps[0] != '\0') return launch_stamped(num_work, p, st, stamps);

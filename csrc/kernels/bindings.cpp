@@ -627,9 +627,25 @@ void gemm_silu(const Tensor& x, const Tensor& w, Tensor& out) {
   run_gemm(dsse::kSiluMul, x, w, ep);
 }
 
+// The KV cache element type of an op call: bf16 (false) or FP8 e4m3fn (true); both caches must agree, and anything
+// else is refused -- no kernel reads a cache dtype it was not instantiated for.  Scales must be positive and finite.
+bool cache_is_f8(const Tensor& k_cache, const Tensor& v_cache, double k_scale, double v_scale) {
+  check_gpu(k_cache, "k_cache");
+  check_gpu(v_cache, "v_cache");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), "k_cache and v_cache must have one dtype");
+  const bool f8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(f8 || k_cache.scalar_type() == at::kBFloat16, "KV cache must be bfloat16 or float8_e4m3fn, got ",
+              k_cache.scalar_type());
+  TORCH_CHECK(k_scale > 0 && v_scale > 0 && std::isfinite(k_scale) && std::isfinite(v_scale),
+              "k_scale / v_scale must be positive and finite");
+  TORCH_CHECK(f8 || (k_scale == 1.0 && v_scale == 1.0), "k_scale / v_scale apply to a float8_e4m3fn KV cache only");
+  return f8;
+}
+
 void gemm_qkv_rope(const Tensor& x, const Tensor& w, const Tensor& positions, const Tensor& slots,
                    const Tensor& rope, Tensor& q_out, Tensor& k_cache, Tensor& v_cache, int64_t nh,
-                   int64_t nkv) {
+                   int64_t nkv, double k_scale, double v_scale, const c10::optional<Tensor>& scratch) {
+  const bool f8 = cache_is_f8(k_cache, v_cache, k_scale, v_scale);
   for (auto* t : {&positions, &slots, &rope}) check_gpu(*t, "metadata");
   check_gpu(q_out, "q_out");
   check_gpu(k_cache, "k_cache");
@@ -657,6 +673,32 @@ void gemm_qkv_rope(const Tensor& x, const Tensor& w, const Tensor& positions, co
   ep.nkv = (int)nkv;
   ep.num_slots = (int)(k_cache.size(0) * dsse::kBS);
   ep.rope_len = (int)rope.size(0);
+  if (f8) {
+    // FP8 cache: the projection in its fp32 store mode (any of the GEMM kernels), then one pass that rotates, stores
+    // q and quantises K / V from the fp32 sums (elementwise.hip qkv_rope_f32_kernel).  The decode hot path is the
+    // folded form (qkv_attention_decode), which quantises inside the attention kernel; where that op falls back to
+    // this one (the register-streaming GEMM of up to 16 rows leaves no slabs) it costs one launch and an fp32 [M, N]
+    // round trip per layer more than the bf16 epilogue (measured: profiles/kv_fp8.md).  `scratch`: the caller's fp32
+    // buffer of at least M x N floats (the engine's split-K slab buffer), so no step allocates.
+    const int M = (int)x.size(0), N = (int)w.size(0);
+    at::Tensor y;
+    if (scratch.has_value() && scratch->numel() >= (int64_t)M * N) {
+      check_gpu(*scratch, "scratch");
+      check_dtype(*scratch, at::kFloat, "scratch");
+      TORCH_CHECK(scratch->is_contiguous(), "scratch must be contiguous");
+      y = scratch->view({-1}).narrow(0, 0, (int64_t)M * N).view({M, N});
+    } else {
+      y = at::empty({M, N}, x.options().dtype(at::kFloat));
+    }
+    dsse::GemmEpi ey{};
+    ey.out = y.data_ptr();
+    ey.ldo = N;
+    run_gemm(dsse::kStoreF32, x, w, ey);
+    DSSE_CHECK_HIP(dsse_qkv_rope_f8(M, y.data_ptr<float>(), (int)nh, (int)nkv, ep.positions, ep.slots, ep.rope,
+                                    q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), ep.num_slots,
+                                    ep.rope_len, (float)(1.0 / k_scale), (float)(1.0 / v_scale), cur_stream()));
+    return;
+  }
   run_gemm(dsse::kQkvRope, x, w, ep);
 }
 
@@ -707,7 +749,9 @@ void rmsnorm(Tensor& resid, const Tensor& w, Tensor& y, double eps, const c10::o
 }
 
 void rope_kv_write(const Tensor& qkv, const Tensor& positions, const Tensor& slots, const Tensor& rope,
-                   Tensor& q_out, Tensor& k_cache, Tensor& v_cache, int64_t nh, int64_t nkv) {
+                   Tensor& q_out, Tensor& k_cache, Tensor& v_cache, int64_t nh, int64_t nkv, double k_scale,
+                   double v_scale) {
+  const bool f8 = cache_is_f8(k_cache, v_cache, k_scale, v_scale);
   check_gpu(qkv, "qkv");
   check_dtype(qkv, at::kBFloat16, "qkv");
   const int T = (int)qkv.size(0);
@@ -715,6 +759,15 @@ void rope_kv_write(const Tensor& qkv, const Tensor& positions, const Tensor& slo
   TORCH_CHECK(positions.numel() >= T && slots.numel() >= T, "metadata too short");
   TORCH_CHECK(q_out.numel() >= (int64_t)T * nh * 128, "q_out too small");
   TORCH_CHECK(k_cache.size(1) == nkv && v_cache.size(1) == nkv, "cache head mismatch");
+  if (f8) {
+    DSSE_CHECK_HIP(dsse_rope_kv_write_f8(T, qkv.data_ptr(), (int)nh, (int)nkv, positions.data_ptr<int>(),
+                                         slots.data_ptr<int>(),
+                                         reinterpret_cast<const float2*>(rope.data_ptr<float>()), q_out.data_ptr(),
+                                         k_cache.data_ptr(), v_cache.data_ptr(), (int)(k_cache.size(0) * dsse::kBS),
+                                         (int)rope.size(0), (float)(1.0 / k_scale), (float)(1.0 / v_scale),
+                                         cur_stream()));
+    return;
+  }
   DSSE_CHECK_HIP(dsse_rope_kv_write(T, qkv.data_ptr(), (int)nh, (int)nkv, positions.data_ptr<int>(),
                                     slots.data_ptr<int>(),
                                     reinterpret_cast<const float2*>(rope.data_ptr<float>()),
@@ -758,11 +811,10 @@ void ring_advance(Tensor& counter) {
 dsse::AttnParams attn_params(int hq, const Tensor& k_cache, const Tensor& v_cache, const Tensor& block_tables,
                              const Tensor& q_start, const Tensor& q_len, const Tensor& ctx_len, const Tensor& work_seq,
                              const Tensor& work_tile, Tensor& out, Tensor& part_o, Tensor& part_ml, int64_t part,
-                             int64_t nparts, int qw, int kwv) {
-  for (const Tensor* t : {&k_cache, &v_cache, (const Tensor*)&out}) {
-    check_gpu(*t, "attention tensor");
-    check_dtype(*t, at::kBFloat16, "attention tensor");
-  }
+                             int64_t nparts, int qw, int kwv, double k_scale = 1.0, double v_scale = 1.0) {
+  const bool f8 = cache_is_f8(k_cache, v_cache, k_scale, v_scale);
+  check_gpu(out, "attention tensor");
+  check_dtype(out, at::kBFloat16, "attention tensor");
   for (auto* t : {&block_tables, &q_start, &q_len, &ctx_len, &work_seq, &work_tile}) {
     check_gpu(*t, "attention metadata");
     check_dtype(*t, at::kInt, "attention metadata");
@@ -805,6 +857,13 @@ dsse::AttnParams attn_params(int hq, const Tensor& k_cache, const Tensor& v_cach
   p.part = (int)part;
   p.nparts = (int)nparts;
   p.scale_log2 = 1.4426950408889634f / sqrtf(128.f);
+  if (f8) {
+    p.kv_f8 = 1;
+    p.scale_log2 *= (float)k_scale;  // scores over stored keys: k_scale folded in
+    p.v_scale = (float)v_scale;
+    p.k_inv = (float)(1.0 / k_scale);
+    p.v_inv = (float)(1.0 / v_scale);
+  }
   const int env_kwv = env_int("attn_kwv", 0);
   p.kwv = (env_kwv == 1 || env_kwv == 2 || env_kwv == 4 || env_kwv == 8) ? env_kwv : 0;
   const int env_pd = env_int("attn_pd", 0);
@@ -824,7 +883,8 @@ void attn_last_arriver(dsse::AttnParams& p, int num_work, const at::Device& dev)
 void paged_attention(int64_t mode, const Tensor& q, const Tensor& k_cache, const Tensor& v_cache,
                      const Tensor& block_tables, const Tensor& q_start, const Tensor& q_len,
                      const Tensor& ctx_len, const Tensor& work_seq, const Tensor& work_tile,
-                     Tensor& out, Tensor& part_o, Tensor& part_ml, int64_t part, int64_t nparts) {
+                     Tensor& out, Tensor& part_o, Tensor& part_ml, int64_t part, int64_t nparts, double k_scale,
+                     double v_scale) {
   check_gpu(q, "q");
   check_dtype(q, at::kBFloat16, "q");
   TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
@@ -834,7 +894,9 @@ void paged_attention(int64_t mode, const Tensor& q, const Tensor& k_cache, const
   if (mode == 2) TORCH_CHECK(hq % hkv == 0 && (hq / hkv == 1 || hq / hkv == 2 || hq / hkv == 4),
                              "flash prefill supports G in {1, 2, 4}");
   dsse::AttnParams p = attn_params(hq, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq, work_tile,
-                                   out, part_o, part_ml, part, nparts, mode == 0 ? 1 : 4, mode == 0 ? 4 : 1);
+                                   out, part_o, part_ml, part, nparts, mode == 0 ? 1 : 4, mode == 0 ? 4 : 1, k_scale,
+                                   v_scale);
+  TORCH_CHECK(!(mode == 2 && p.kv_f8), "flash prefill (mode 2) has no float8_e4m3fn KV cache form: use mode 1");
   p.q = reinterpret_cast<const bf16*>(q.data_ptr());
   const int num_work = (int)work_seq.numel();
   if (mode == 2) {
@@ -873,6 +935,8 @@ void flash_prefill_split(const Tensor& q, const Tensor& k_cache, const Tensor& v
   TORCH_CHECK(nslots >= 0 && part_o.numel() >= nslots * hkv * hq / hkv * 64 * 128 &&
                   part_ml.numel() >= nslots * hkv * hq / hkv * 64 * 2, "part_o / part_ml too small for nslots");
   Tensor ws = work.narrow(0, 0, nw), wt = work.narrow(0, nw, nw);
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 && v_cache.scalar_type() == at::kBFloat16,
+              "flash prefill has no float8_e4m3fn KV cache form: use paged_attention mode 1");
   dsse::AttnParams p = attn_params(hq, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, ws, wt, out, part_o,
                                    part_ml, 32, 1, 4, 1);
   p.q = reinterpret_cast<const bf16*>(q.data_ptr());
@@ -896,7 +960,7 @@ int64_t qkv_attention_decode(const Tensor& x, const Tensor& w, const Tensor& pos
                              int64_t nkv, Tensor& slabs, const Tensor& block_tables, const Tensor& q_start,
                              const Tensor& q_len, const Tensor& ctx_len, const Tensor& work_seq,
                              const Tensor& work_tile, Tensor& out, Tensor& part_o, Tensor& part_ml, int64_t part,
-                             int64_t nparts) {
+                             int64_t nparts, double k_scale, double v_scale) {
   check_gpu(x, "x");
   check_gpu(w, "w");
   check_gpu(slabs, "slabs");
@@ -922,9 +986,9 @@ int64_t qkv_attention_decode(const Tensor& x, const Tensor& w, const Tensor& pos
   auto o3 = out.view({-1, nh, 128});
   const bool group_ok = nkv > 0 && nh % nkv == 0 && (nh / nkv == 1 || nh / nkv == 2 || nh / nkv == 4);  // attention.hip
   if ((S <= 0 || !group_ok || slabs.numel() < (int64_t)S * M * N || env_int("fused_qkv_attn", 1) == 0)) {
-    gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv);
+    gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale, slabs);
     paged_attention(0, q3, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq, work_tile, o3, part_o,
-                    part_ml, part, nparts);
+                    part_ml, part, nparts, k_scale, v_scale);
     return 0;
   }
   check_dtype(x, at::kBFloat16, "x");
@@ -940,7 +1004,7 @@ int64_t qkv_attention_decode(const Tensor& x, const Tensor& w, const Tensor& pos
   TORCH_CHECK(k_cache.size(1) == nkv, "k_cache heads must be nkv");
   TORCH_CHECK(o3.size(0) == M, "out must hold the M query rows");
   dsse::AttnParams p = attn_params((int)nh, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq,
-                                   work_tile, o3, part_o, part_ml, part, nparts, 1, 4);
+                                   work_tile, o3, part_o, part_ml, part, nparts, 1, 4, k_scale, v_scale);
   dsse::GemmEpi ep{};
   const void* X = x.data_ptr();
   float* sl = slabs.data_ptr<float>();
@@ -1691,28 +1755,29 @@ TORCH_LIBRARY(dsse, m) {
   m.def("gemm_resid(Tensor x, Tensor w, Tensor(a!) resid) -> ()");
   m.def("gemm_silu(Tensor x, Tensor w, Tensor(a!) out) -> ()");
   m.def("gemm_qkv_rope(Tensor x, Tensor w, Tensor positions, Tensor slots, Tensor rope, Tensor(a!) q_out, "
-        "Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv) -> ()");
+        "Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv, float k_scale=1.0, float v_scale=1.0, "
+        "Tensor(d!)? scratch=None) -> ()");
   m.def("rmsnorm(Tensor(a!) resid, Tensor w, Tensor(b!) y, float eps, Tensor? delta=None, Tensor? embed=None, "
         "Tensor? ids=None, Tensor? part=None, int nsplit=0) -> ()");
   m.def("gemm_resid_split(Tensor x, Tensor w, Tensor(a!) resid, Tensor(b!) part) -> int");
   m.def("gemm_out_split(Tensor x, Tensor w, Tensor(a!) out, Tensor(b!) part) -> int");
   m.def("refresh_env() -> ()", &refresh_env);
   m.def("rope_kv_write(Tensor qkv, Tensor positions, Tensor slots, Tensor rope, Tensor(a!) q_out, "
-        "Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv) -> ()");
+        "Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("silu_mul(Tensor gu, Tensor(a!) h) -> ()");
   m.def("decode_prep(Tensor active, Tensor positions, Tensor block_tables, Tensor(a!) slots, "
         "Tensor(b!) ctx_len, Tensor(c!) q_len, int num_blocks=2147483647) -> ()");
   m.def("ring_advance(Tensor(a!) counter) -> ()");
   m.def("paged_attention(int mode, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor q_start, Tensor q_len, Tensor ctx_len, Tensor work_seq, Tensor work_tile, Tensor(a!) out, "
-        "Tensor(b!) part_o, Tensor(c!) part_ml, int part, int nparts) -> ()");
+        "Tensor(b!) part_o, Tensor(c!) part_ml, int part, int nparts, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("flash_prefill_split(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_start, "
         "Tensor q_len, Tensor ctx_len, Tensor work, Tensor comb, Tensor(a!) out, Tensor(b!) part_o, "
         "Tensor(c!) part_ml, int nslots) -> ()");
   m.def("qkv_attention_decode(Tensor x, Tensor w, Tensor positions, Tensor slots, Tensor rope, Tensor(a!) q_out, "
         "Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv, Tensor(d!) slabs, Tensor block_tables, "
         "Tensor q_start, Tensor q_len, Tensor ctx_len, Tensor work_seq, Tensor work_tile, Tensor(e!) out, "
-        "Tensor(f!) part_o, Tensor(g!) part_ml, int part, int nparts) -> int");
+        "Tensor(f!) part_o, Tensor(g!) part_ml, int part, int nparts, float k_scale=1.0, float v_scale=1.0) -> int");
   m.def("sample_candidates(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, "
         "Tensor positions, Tensor? active, Tensor(a!) cand, int vocab_offset=0) -> ()");
   m.def("sample_pick(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring=None, "

@@ -17,6 +17,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define DEV __device__ __forceinline__
@@ -56,6 +57,51 @@ DEV bf16x8 ld_buf_bf16x8(__amdgpu_buffer_rsrc_t r, uint32_t off) {
 // Non-temporal 16-byte load for once-read streams (weights, KV pages).
 DEV bf16x8 ld_nt_bf16x8(const bf16* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p));
+}
+
+// ---- FP8 KV cache (OCP e4m3fn on gfx950, the encoding of torch.float8_e4m3fn) ----
+// A cache element is a raw byte.  Stored value = x / scale, clamped to the finite range +-448 in fp32 (so nothing
+// depends on the convert instruction's saturation mode) and rounded once, to nearest even, by v_cvt_pk_fp8_f32.
+// Every e4m3 value is exact in bf16, so the readers widen the bytes in registers and feed the bf16 MFMAs.
+typedef unsigned char f8;
+constexpr float kF8Max = 448.f;
+
+DEV f8 quant_f8(float x, float inv_scale) {
+  const float y = fminf(fmaxf(x * inv_scale, -kF8Max), kF8Max);
+  return (f8)(__builtin_amdgcn_cvt_pk_fp8_f32(y, y, 0, false) & 0xFF);
+}
+// 8 values -> 8 bytes (element j in byte j)
+DEV uint2 quant_f8x8(const float (&x)[8], float inv_scale) {
+  float y[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = fminf(fmaxf(x[j] * inv_scale, -kF8Max), kF8Max);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+  return make_uint2((unsigned)lo, (unsigned)hi);
+}
+DEV float f8_to_f(f8 b) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false)[0]; }
+// 4 bytes of `w` -> elements [4 half, 4 half + 4) of a bf16x8 (exact)
+DEV void widen_f8x4(unsigned w, bf16x8& o, int half) {
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  o[4 * half + 0] = (bf16)a[0];
+  o[4 * half + 1] = (bf16)a[1];
+  o[4 * half + 2] = (bf16)b[0];
+  o[4 * half + 3] = (bf16)b[1];
+}
+DEV bf16x8 widen_f8x8(uint2 v) {
+  bf16x8 o;
+  widen_f8x4(v.x, o, 0);
+  widen_f8x4(v.y, o, 1);
+  return o;
+}
+// Store one K / V element (an fp32 value before any rounding) as the cache's element type: the one definition the
+// cache writers share (elementwise.hip rope_kv_rows / v_page_write / qkv_rope_f32_kernel, attention.hip's folded write).
+template <typename KV>
+DEV void store_kv(KV* dst, float x, float inv_scale) {
+  if constexpr (sizeof(KV) == 1) *dst = quant_f8(x, inv_scale);
+  else *dst = f2bf(x);
 }
 
 template <typename T>

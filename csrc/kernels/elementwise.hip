@@ -103,9 +103,12 @@ rmsnorm_kernel(float* __restrict__ resid, int H, const bf16* __restrict__ delta,
 // qkv: [T, (hq + 2 hkv) * 128] bf16 in the engine's permuted column order (inside each 16-column
 // tile j of a head: columns 0..7 = dims 8j..8j+7, columns 8..15 = dims 64+8j..64+8j+7).
 // A token's rows: each thread rotates 8 pairs of one (unit, tile j) with 16-byte loads and stores.
+// KV = bf16, or f8 (FP8 cache: K rows are quantised from the rotated fp32 value with 1 / k_scale, 8-byte stores).
+template <typename KV>
 DEV void rope_kv_rows(const bf16* __restrict__ qkv, int hq, int hkv, const int* __restrict__ positions,
                       const int* __restrict__ slots, const float2* __restrict__ rope, bf16* __restrict__ q_out,
-                      bf16* __restrict__ k_cache, int num_slots, int rope_len, int t) {
+                      KV* __restrict__ k_cache, int num_slots, int rope_len, int t, float k_inv) {
+  constexpr bool F8 = sizeof(KV) == 1;
   const int ncols = (hq + 2 * hkv) * 128;
   const bf16* row = qkv + (size_t)t * ncols;
   const int pos = DSSE_IDX(positions[t], rope_len, 0);
@@ -114,12 +117,37 @@ DEV void rope_kv_rows(const bf16* __restrict__ qkv, int hq, int hkv, const int* 
   const int nrot = (hq + hkv) * 8;  // q and k heads x 8 column tiles (V: v_page_write)
   for (int idx = threadIdx.x; idx < nrot; idx += blockDim.x) {
     const int u = idx >> 3, j = idx & 7;
-    bf16* dst = u < hq ? q_out + ((size_t)t * hq + u) * 128
-                       : (slot >= 0 ? k_cache + (((size_t)blk * hkv + (u - hq)) * kPageTok + off) * 128 : nullptr);
-    if (dst == nullptr) continue;
+    bf16* dst = nullptr;
+    KV* kdst = nullptr;  // F8: the key row (q rows stay bf16)
+    if constexpr (F8) {
+      if (u < hq) dst = q_out + ((size_t)t * hq + u) * 128;
+      else if (slot >= 0) kdst = k_cache + (((size_t)blk * hkv + (u - hq)) * kPageTok + off) * 128;
+      if (dst == nullptr && kdst == nullptr) continue;
+    } else {
+      dst = u < hq ? q_out + ((size_t)t * hq + u) * 128
+                   : (slot >= 0 ? k_cache + (((size_t)blk * hkv + (u - hq)) * kPageTok + off) * 128 : nullptr);
+      if (dst == nullptr) continue;
+    }
     const bf16x8 x1 = ld_bf16x8(row + u * 128 + 16 * j);
     const bf16x8 x2 = ld_bf16x8(row + u * 128 + 16 * j + 8);
     const float4* cs4 = reinterpret_cast<const float4*>(rope + (size_t)pos * 64 + 8 * j);
+    if constexpr (F8) {
+      if (kdst != nullptr) {
+        float f1[8], f2[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float4 cs = cs4[e];
+          const float a0 = bf2f(x1[2 * e]), b0 = bf2f(x2[2 * e]), a1 = bf2f(x1[2 * e + 1]), b1 = bf2f(x2[2 * e + 1]);
+          f1[2 * e] = a0 * cs.x - b0 * cs.y;
+          f2[2 * e] = b0 * cs.x + a0 * cs.y;
+          f1[2 * e + 1] = a1 * cs.z - b1 * cs.w;
+          f2[2 * e + 1] = b1 * cs.z + a1 * cs.w;
+        }
+        *reinterpret_cast<uint2*>(kdst + 8 * j) = quant_f8x8(f1, k_inv);
+        *reinterpret_cast<uint2*>(kdst + 64 + 8 * j) = quant_f8x8(f2, k_inv);
+        continue;
+      }
+    }
     bf16x8 o1, o2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -142,8 +170,11 @@ DEV void rope_kv_rows(const bf16* __restrict__ qkv, int hq, int hkv, const int* 
 // d as 4 x 16-byte stores in the vperm token order.  Other groups (page boundaries, padding, scattered slots) fall
 // back to per-element stores.
 // (rows t0 .. t0 + 31, kv head h, dim d = the thread's index in its 128-thread half; a wave never spans two heads)
+// FP8 cache (KV = f8): the page row is 32 bytes, written as 4 x 8-byte runs; values quantised with 1 / v_scale.
+template <typename KV>
 DEV void v_page_write(const bf16* __restrict__ qkv, int T, int hq, int hkv, const int* __restrict__ slots,
-                      bf16* __restrict__ v_cache, int num_slots, int t0, int h, int d) {
+                      KV* __restrict__ v_cache, int num_slots, int t0, int h, int d, float v_inv) {
+  constexpr bool F8 = sizeof(KV) == 1;
   const int ncols = (hq + 2 * hkv) * 128;
   const int lane = threadIdx.x & 63;
   const int tl = t0 + (lane & 31);
@@ -158,35 +189,85 @@ DEV void v_page_write(const bf16* __restrict__ qkv, int T, int hq, int hkv, cons
     bf16 v[kPageTok];
 #pragma unroll
     for (int i = 0; i < kPageTok; ++i) v[i] = src[(size_t)i * ncols];
-    bf16x8 o[4];
+    KV* dst = v_cache + (((size_t)(s0 / kPageTok) * hkv + h) * 128 + d) * kPageTok;
+    if constexpr (F8) {
+      float o[4][8];
 #pragma unroll
-    for (int i = 0; i < kPageTok; ++i) o[vperm_tok(i) >> 3][vperm_tok(i) & 7] = v[i];
-    bf16* dst = v_cache + (((size_t)(s0 / kPageTok) * hkv + h) * 128 + d) * kPageTok;
+      for (int i = 0; i < kPageTok; ++i) o[vperm_tok(i) >> 3][vperm_tok(i) & 7] = bf2f(v[i]);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<bf16x8*>(dst + 8 * q) = o[q];
+      for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(dst + 8 * q) = quant_f8x8(o[q], v_inv);
+    } else {
+      bf16x8 o[4];
+#pragma unroll
+      for (int i = 0; i < kPageTok; ++i) o[vperm_tok(i) >> 3][vperm_tok(i) & 7] = v[i];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *reinterpret_cast<bf16x8*>(dst + 8 * q) = o[q];
+    }
     return;
   }
   for (int i = 0; i < kPageTok && t0 + i < T; ++i) {
     const int sl = __shfl(my_slot, i);
     if (sl < 0) continue;
-    v_cache[(((size_t)(sl / kPageTok) * hkv + h) * 128 + d) * kPageTok + vperm_tok(sl % kPageTok)] = src[(size_t)i * ncols];
+    KV* vd = v_cache + (((size_t)(sl / kPageTok) * hkv + h) * 128 + d) * kPageTok + vperm_tok(sl % kPageTok);
+    if constexpr (F8) *vd = quant_f8(bf2f(src[(size_t)i * ncols]), v_inv);
+    else *vd = src[(size_t)i * ncols];
   }
 }
 
 // One launch for both: blocks [0, T) rotate q / k of one token each (rope_kv_rows), the blocks after
 // them write V page rows, two kv heads per 256-thread block.
+template <typename KV>
 __global__ void __launch_bounds__(256)
 rope_kv_v_kernel(const bf16* __restrict__ qkv, int T, int hq, int hkv, const int* __restrict__ positions,
                  const int* __restrict__ slots, const float2* __restrict__ rope, bf16* __restrict__ q_out,
-                 bf16* __restrict__ k_cache, bf16* __restrict__ v_cache, int num_slots, int rope_len) {
+                 KV* __restrict__ k_cache, KV* __restrict__ v_cache, int num_slots, int rope_len, float k_inv,
+                 float v_inv) {
   if ((int)blockIdx.x < T) {
-    rope_kv_rows(qkv, hq, hkv, positions, slots, rope, q_out, k_cache, num_slots, rope_len, blockIdx.x);
+    rope_kv_rows<KV>(qkv, hq, hkv, positions, slots, rope, q_out, k_cache, num_slots, rope_len, blockIdx.x, k_inv);
     return;
   }
   const int vb = blockIdx.x - T, hpairs = (hkv + 1) / 2;
   const int h = 2 * (vb % hpairs) + (threadIdx.x >> 7);
   if (h >= hkv) return;  // wave-uniform (128-thread halves)
-  v_page_write(qkv, T, hq, hkv, slots, v_cache, num_slots, (vb / hpairs) * kPageTok, h, threadIdx.x & 127);
+  v_page_write<KV>(qkv, T, hq, hkv, slots, v_cache, num_slots, (vb / hpairs) * kPageTok, h, threadIdx.x & 127, v_inv);
+}
+
+// ---- FP8 cache: RoPE + q store + quantised paged KV write from the QKV projection's fp32 output ----------------
+// y: [M, (hq + 2 hkv) * 128] fp32 sums in the engine's permuted column order (any decode / tiled GEMM in its fp32
+// store mode).  K and V are quantised from the fp32 rotated / summed value -- one rounding, as ops/reference.py
+// defines it.  One thread per (row, 16-column tile, j < 8): columns 16 tile + j and + 8 (the rotary partners).
+__global__ void __launch_bounds__(256)
+qkv_rope_f32_kernel(const float* __restrict__ y, int M, int hq, int hkv, const int* __restrict__ positions,
+                    const int* __restrict__ slots, const float2* __restrict__ rope, bf16* __restrict__ q_out,
+                    f8* __restrict__ k_cache, f8* __restrict__ v_cache, int num_slots, int rope_len, float k_inv,
+                    float v_inv) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int tiles = (hq + 2 * hkv) * 8;
+  if (idx >= M * tiles * 8) return;
+  const int j = idx & 7, tile = (idx >> 3) % tiles, m = (idx >> 3) / tiles;
+  const size_t base = (size_t)m * tiles * 16 + tile * 16 + j;
+  const float a = y[base], b = y[base + 8];
+  const int unit = tile >> 3, tj = tile & 7;
+  const int d = 8 * tj + j;  // a: head dim d, b: d + 64
+  const int s = slots[m] < 0 ? -1 : DSSE_IDX(slots[m], num_slots, -1);
+  const int blk = s >= 0 ? s / kPageTok : 0, off = s >= 0 ? s % kPageTok : 0;
+  if (unit < hq + hkv) {
+    const float2 cs = rope[(size_t)DSSE_IDX(positions[m], rope_len, 0) * 64 + d];
+    const float r1 = a * cs.x - b * cs.y, r2 = b * cs.x + a * cs.y;
+    if (unit < hq) {
+      bf16* q = q_out + ((size_t)m * hq + unit) * 128;
+      q[d] = f2bf(r1);
+      q[64 + d] = f2bf(r2);
+    } else if (s >= 0) {
+      f8* k = k_cache + (((size_t)blk * hkv + (unit - hq)) * kPageTok + off) * 128;
+      store_kv(k + d, r1, k_inv);
+      store_kv(k + 64 + d, r2, k_inv);
+    }
+  } else if (s >= 0) {
+    f8* v = v_cache + ((size_t)blk * hkv + (unit - hq - hkv)) * 128 * kPageTok + vperm_tok(off);
+    store_kv(v + (size_t)d * kPageTok, a, v_inv);
+    store_kv(v + (size_t)(64 + d) * kPageTok, b, v_inv);
+  }
 }
 
 // ---- SiLU·mul over the interleaved gate/up output of a library GEMM (prefill) ---------------
@@ -279,9 +360,34 @@ extern "C" hipError_t dsse_rope_kv_write(int T, const void* qkv, int hq, int hkv
                                          hipStream_t st) {
   if (T <= 0) return hipSuccess;
   const int vblocks = (T + kPageTok - 1) / kPageTok * ((hkv + 1) / 2);
-  hipLaunchKernelGGL(rope_kv_v_kernel, dim3(T + vblocks), dim3(256), 0, st, reinterpret_cast<const bf16*>(qkv), T,
+  hipLaunchKernelGGL(rope_kv_v_kernel<bf16>, dim3(T + vblocks), dim3(256), 0, st, reinterpret_cast<const bf16*>(qkv), T,
                      hq, hkv, positions, slots, rope, reinterpret_cast<bf16*>(q_out), reinterpret_cast<bf16*>(k_cache),
-                     reinterpret_cast<bf16*>(v_cache), num_slots, rope_len);
+                     reinterpret_cast<bf16*>(v_cache), num_slots, rope_len, 1.f, 1.f);
+  return hipGetLastError();
+}
+
+// FP8 (e4m3) cache form of dsse_rope_kv_write: k_inv = 1 / k_scale, v_inv = 1 / v_scale.
+extern "C" hipError_t dsse_rope_kv_write_f8(int T, const void* qkv, int hq, int hkv, const int* positions,
+                                            const int* slots, const float2* rope, void* q_out, void* k_cache,
+                                            void* v_cache, int num_slots, int rope_len, float k_inv, float v_inv,
+                                            hipStream_t st) {
+  if (T <= 0) return hipSuccess;
+  const int vblocks = (T + kPageTok - 1) / kPageTok * ((hkv + 1) / 2);
+  hipLaunchKernelGGL(rope_kv_v_kernel<f8>, dim3(T + vblocks), dim3(256), 0, st, reinterpret_cast<const bf16*>(qkv), T,
+                     hq, hkv, positions, slots, rope, reinterpret_cast<bf16*>(q_out), reinterpret_cast<f8*>(k_cache),
+                     reinterpret_cast<f8*>(v_cache), num_slots, rope_len, k_inv, v_inv);
+  return hipGetLastError();
+}
+
+// FP8 cache: the QKV projection's epilogue from its fp32 output y [M, (hq + 2 hkv) * 128] (qkv_rope_f32_kernel).
+extern "C" hipError_t dsse_qkv_rope_f8(int M, const float* y, int hq, int hkv, const int* positions, const int* slots,
+                                       const float2* rope, void* q_out, void* k_cache, void* v_cache, int num_slots,
+                                       int rope_len, float k_inv, float v_inv, hipStream_t st) {
+  if (M <= 0) return hipSuccess;
+  const long threads = (long)M * (hq + 2 * hkv) * 64;
+  hipLaunchKernelGGL(qkv_rope_f32_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, y, M, hq, hkv,
+                     positions, slots, rope, reinterpret_cast<bf16*>(q_out), reinterpret_cast<f8*>(k_cache),
+                     reinterpret_cast<f8*>(v_cache), num_slots, rope_len, k_inv, v_inv);
   return hipGetLastError();
 }
 

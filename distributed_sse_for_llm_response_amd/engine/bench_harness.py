@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import math
+import os
 import time
 
 import numpy as np
@@ -102,7 +103,11 @@ class PacedStubEngine:
 
 
 def _build_runner(model: str, device, streams: int, prompt_len: int, total_steps: int, tp: int, use_graphs: bool,
-                  rank: int, world: int, comm: TPComm | None = None):
+                  rank: int, world: int, comm: TPComm | None = None, kv_cache_dtype: str | None = None):
+    # kv_cache_dtype: None = the serving key KV_CACHE_DTYPE from the environment (auto = bf16), so the flagship
+    # benchmark times an fp8 cache without a flag of its own
+    if kv_cache_dtype is None:
+        kv_cache_dtype = os.environ.get("KV_CACHE_DTYPE") or "auto"
     # on CPU the 7B architecture is replaced by the tiny one (plumbing runs); named small configs are kept
     cfg = get_config(model) if device.type == "cuda" or not model.startswith("mistral-7b") else TINY
     if comm is None:
@@ -116,7 +121,7 @@ def _build_runner(model: str, device, streams: int, prompt_len: int, total_steps
     max_len = prompt_len + total_steps + 2 * PAGE
     nblk = streams * (blocks_needed(max_len) + 1) + 4
     runner = ModelRunner(w, num_blocks=nblk, max_batch=streams, max_model_len=max_len, device=device, comm=comm,
-                         use_graphs=use_graphs)
+                         use_graphs=use_graphs, kv_cache_dtype=kv_cache_dtype)
     return cfg, runner
 
 

@@ -8,6 +8,11 @@ Layout (one tensor per K and V for all layers, so a layer's cache is a contiguou
 Pages are 32 tokens.  At TP=1 Mistral-7B needs 128 KiB per token, so 100 GB of the 288 GB HBM holds
 ~780k tokens (about 190 sequences of 4k context per GPU).  The cache is zero-initialised so keys
 past a sequence's end inside its last page are finite (they are masked, but 0·NaN would poison PV).
+
+``dtype=torch.float8_e4m3fn`` (``kv_cache_dtype="fp8"``) stores one byte per element in the same shapes and element
+order: a key row is 128 bytes, a token costs 64 KiB, and the same budget holds twice the pages.  Stored value =
+x / scale with per-layer fp32 scalars ``k_scale`` / ``v_scale`` (default 1.0; ops/reference.py ``quantize_kv``).
+Nothing above the cache -- allocator, block tables, slots, prefix-cache hashes -- knows the dtype.
 """
 from __future__ import annotations
 
@@ -19,20 +24,43 @@ import torch
 
 PAGE = 32
 
+from ..serving.config import KV_CACHE_DTYPES  # ("auto", "bf16", "fp8", "fp8_e4m3"): auto = bf16; fp8 = fp8_e4m3
+
+
+def kv_cache_torch_dtype(name) -> torch.dtype:
+    """The cache element type of a ``kv_cache_dtype`` option (or a torch dtype, passed through)."""
+    if isinstance(name, torch.dtype):
+        if name not in (torch.bfloat16, torch.float8_e4m3fn):
+            raise ValueError(f"KV cache dtype must be bfloat16 or float8_e4m3fn, got {name}")
+        return name
+    key = str(name or "auto").strip().lower()
+    if key not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be one of {', '.join(KV_CACHE_DTYPES)}; got {name!r}")
+    return torch.float8_e4m3fn if key.startswith("fp8") else torch.bfloat16
+
 
 class KVCache:
     def __init__(self, num_layers: int, num_blocks: int, nkv: int, device, dtype=torch.bfloat16):
+        dtype = kv_cache_torch_dtype(dtype)
         self.num_layers, self.num_blocks, self.nkv = num_layers, num_blocks, nkv
+        self.dtype = dtype
         self.k = torch.zeros(num_layers, num_blocks, nkv, PAGE, 128, device=device, dtype=dtype)
         self.v = torch.zeros(num_layers, num_blocks, nkv, 128, PAGE, device=device, dtype=dtype)
+        # per-layer dequantisation scales of an fp8 cache (host floats: constants of every captured graph)
+        self.k_scale = [1.0] * num_layers
+        self.v_scale = [1.0] * num_layers
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.dtype == torch.float8_e4m3fn
 
     @staticmethod
-    def bytes_per_block(num_layers: int, nkv: int) -> int:
-        return 2 * num_layers * nkv * PAGE * 128 * 2
+    def bytes_per_block(num_layers: int, nkv: int, dtype=torch.bfloat16) -> int:
+        return 2 * num_layers * nkv * PAGE * 128 * kv_cache_torch_dtype(dtype).itemsize
 
     @classmethod
-    def blocks_for_budget(cls, budget_bytes: int, num_layers: int, nkv: int) -> int:
-        return max(1, budget_bytes // cls.bytes_per_block(num_layers, nkv))
+    def blocks_for_budget(cls, budget_bytes: int, num_layers: int, nkv: int, dtype=torch.bfloat16) -> int:
+        return max(1, budget_bytes // cls.bytes_per_block(num_layers, nkv, dtype))
 
 
 def page_hashes(tokens, prev: bytes = b"", first: int = 0) -> list:

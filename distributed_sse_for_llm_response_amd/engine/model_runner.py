@@ -189,7 +189,8 @@ class PrefillSeq:
 
 class ModelRunner:
     def __init__(self, w: EngineWeights, num_blocks: int, max_batch: int = 64, max_model_len: int = 4096,
-                 max_prefill_tokens: int = 8192, device="cuda", comm: TPComm | None = None, use_graphs=None):
+                 max_prefill_tokens: int = 8192, device="cuda", comm: TPComm | None = None, use_graphs=None,
+                 kv_cache_dtype="auto"):
         self.w, self.cfg = w, w.cfg
         self.device = torch.device(device)
         self.comm = comm or TPComm()
@@ -201,7 +202,14 @@ class ModelRunner:
         cfg, dev = self.cfg, self.device
         H = cfg.hidden_size
         nh, nkv, F, V = w.nh, w.nkv, w.ffn, w.vocab_local
-        self.kv = KVCache(cfg.num_layers, num_blocks, nkv, dev)
+        # kv_cache_dtype "fp8": float8_e4m3fn pages (half the bytes per token), quantised with the layers' k_scale /
+        # v_scale by the cache writers and widened in registers by the attention kernels (every captured graph then
+        # holds the fp8 ops, the scales as constants).  Prompt attention then runs on the paged prefill kernel (mode
+        # 1): the flash kernel has no fp8 form.  Its work items are 64 / G query tokens (4 tiles of 16 / G).
+        self.kv = KVCache(cfg.num_layers, num_blocks, nkv, dev, dtype=kv_cache_dtype)
+        for li, L in enumerate(w.layers):
+            self.kv.k_scale[li], self.kv.v_scale[li] = float(L.k_scale), float(L.v_scale)
+        self.attn_tile = PREFILL_TILE if not self.kv.is_fp8 else 64 // (nh // nkv)
         self.rope = rope_table(max(cfg.max_position, max_model_len + 1), cfg.rope_theta, dev)
         Bm = max_batch
         i32 = dict(device=dev, dtype=torch.int32)
@@ -374,7 +382,25 @@ class ModelRunner:
         ops.qkv_attention_decode(x, L.wqkv_t, self.positions[r], self.slots[r], self.rope, self.q[r], self.kv.k[li],
                                  self.kv.v[li], nh, nkv, self.split_part, self.block_tables[r], self.q_start[r],
                                  self.q_len[r], self.ctx_len[r], self.work_seq[r], self.work_tile[r], self.attn[r],
-                                 self.part_o, self.part_ml, part, nparts)
+                                 self.part_o, self.part_ml, part, nparts, *self._kv_scales(li))
+
+    def _kv_scales(self, li: int) -> tuple:
+        """(k_scale, v_scale) of layer li's cache: trailing arguments of the cache ops (1.0, 1.0 for bf16)."""
+        return (self.kv.k_scale[li], self.kv.v_scale[li]) if self.kv.is_fp8 else (1.0, 1.0)
+
+    def _prefill_attention(self, li: int, q, attn, d: dict, split: bool = False) -> None:
+        """Prompt attention of layer li over the packed chunk rows: the flash kernel (64-query tiles; its key split
+        when the plan has slots), or -- fp8 cache -- the paged prefill kernel on work items of attn_tile queries."""
+        kc, vc = self.kv.k[li], self.kv.v[li]
+        if self.kv.is_fp8:
+            ops.paged_attention(1, q, kc, vc, d["bt"], d["qs"], d["ql"], d["ctx"], d["ws"], d["wt"], attn,
+                                self.part_o, self.part_ml, d["part"], 1, *self._kv_scales(li))
+        elif split and d.get("fslots"):
+            ops.flash_prefill_split(q, kc, vc, d["bt"], d["qs"], d["ql"], d["ctx"], d["fw"], d["fc"], attn, d["fpo"],
+                                    d["fpm"], d["fslots"])
+        else:
+            ops.paged_attention(2, q, kc, vc, d["bt"], d["qs"], d["ql"], d["ctx"], d["ws"], d["wt"], attn,
+                                self.part_o, self.part_ml, d["part"], 1)
 
     def _resid_proj(self, a, wt, resid, norm_w, x, tmp) -> None:
         """resid += a·wᵀ (TP: all-reduced), then x = RMSNorm(resid)·norm_w.  TP = 1: split-K slabs (if the GEMM
@@ -1009,14 +1035,15 @@ class ModelRunner:
             ctx_len.append(s.start_pos + m)
             bt[i, : len(s.block_table)] = torch.from_numpy(table.astype(np.int32))
             # flash prefill: heaviest (most keys) 64-query tiles first, so the causal tail balances over the CUs
-            items += [(-(s.start_pos + min(m, (t + 1) * PREFILL_TILE)), i, t) for t in range(math.ceil(m / PREFILL_TILE))]
+            tile = self.attn_tile
+            items += [(-(s.start_pos + min(m, (t + 1) * tile)), i, t) for t in range(math.ceil(m / tile))]
             row += m
         items.sort()
         work_seq = [i for _, i, _ in items]
         work_tile = [t for _, _, t in items]
         T = row
         plan = None
-        if split:
+        if split and not self.kv.is_fp8:
             plan = flash_split_plan([(i, t, -(-(-k) // PREFILL_TILE)) for k, i, t in items], self.w.nkv)
         fw, fc = (plan[0], plan[1]) if plan else (np.zeros(0, np.int32), np.zeros(0, np.int32))
         empty = np.zeros(0, dtype=np.int64)
@@ -1135,13 +1162,9 @@ class ModelRunner:
             # at 512 rows (gemm_qkv_rope, one launch fewer) 9.21-9.37 vs 9.15-9.33 ms TTFT, alternating
             # (profiles/r6/ttft512_qkv_fused_ab_r6.log)
             self._proj(x, L.wqkv_t, qkv)
-            ops.rope_kv_write(qkv, d["pos"], d["slots"], self.rope, q, self.kv.k[li], self.kv.v[li], nh, nkv)
-            if d.get("fslots"):
-                ops.flash_prefill_split(q, self.kv.k[li], self.kv.v[li], d["bt"], d["qs"], d["ql"], d["ctx"],
-                                        d["fw"], d["fc"], attn, d["fpo"], d["fpm"], d["fslots"])
-            else:
-                ops.paged_attention(2, q, self.kv.k[li], self.kv.v[li], d["bt"], d["qs"], d["ql"], d["ctx"], d["ws"],
-                                    d["wt"], attn, self.part_o, self.part_ml, d["part"], 1)
+            ops.rope_kv_write(qkv, d["pos"], d["slots"], self.rope, q, self.kv.k[li], self.kv.v[li], nh, nkv,
+                              *self._kv_scales(li))
+            self._prefill_attention(li, q, attn, d, split=True)
             w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
             self._prefill_post_attention(T, attn.view(T, nh * 128), L, w_next, resid, x, h, tmp)
 
@@ -1255,12 +1278,11 @@ class ModelRunner:
         for li, L in enumerate(w.layers):
             kc, vc = self.kv.k[li], self.kv.v[li]
             self._proj(x, L.wqkv_t, qkv)
-            ops.rope_kv_write(qkv, pos, slots, self.rope, q, kc, vc, nh, nkv)
+            ops.rope_kv_write(qkv, pos, slots, self.rope, q, kc, vc, nh, nkv, *self._kv_scales(li))
             ops.paged_attention(0, q[r], kc, vc, self.block_tables[r], self.q_start[r], self.q_len[r],
                                 self.ctx_len[r], self.work_seq[r], self.work_tile[r], attn[r], self.part_o,
-                                self.part_ml, dpart, dnparts)
-            ops.paged_attention(2, q, kc, vc, d["bt"], d["qs"], d["ql"], d["ctx"], d["ws"], d["wt"], attn,
-                                self.part_o, self.part_ml, d["part"], 1)
+                                self.part_ml, dpart, dnparts, *self._kv_scales(li))
+            self._prefill_attention(li, q, attn, d)
             self._resid_proj(attn.view(M, nh * 128), L.wo_t, resid, L.ffn_norm, x, tmp)
             self._gate_up(x, L, h)
             w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
@@ -1284,7 +1306,8 @@ class _PrefillStatic:
         w, cfg, dev = runner.w, runner.cfg, runner.device
         nh, nkv, F, H = w.nh, w.nkv, w.ffn, cfg.hidden_size
         self.ns = PREFILL_GRAPH_SEQS
-        self.nw = tmax // PREFILL_TILE + self.ns  # work items: sum of ceil(q_len / 64) <= T / 64 + seqs
+        self.tile = runner.attn_tile  # query tokens per prompt-attention work item (64; fp8 cache: 64 / G)
+        self.nw = tmax // self.tile + self.ns  # work items: sum of ceil(q_len / tile) <= T / tile + seqs
         self.mb = runner.max_blocks
         n1 = self.ns + 1
         self.off = {}
@@ -1333,7 +1356,7 @@ class _PrefillStatic:
         return self._meta("samp")
 
     def views(self, tb: int) -> dict:
-        nwb = tb // PREFILL_TILE + self.ns
+        nwb = tb // self.tile + self.ns
         d = {"ids": self._meta("ids")[:tb], "pos": self._meta("pos")[:tb], "slots": self._meta("slots")[:tb],
              "qs": self._meta("qs"), "ql": self._meta("ql"), "ctx": self._meta("ctx"),
              "ws": self._meta("ws")[:nwb], "wt": self._meta("wt")[:nwb],
@@ -1374,8 +1397,8 @@ class _PrefillStatic:
             bt[i, :len(s.block_table)] = s.block_table
             qs[i], ql[i], ctx[i] = row0 + row, n, s.start_pos + n
             # flash prefill: heaviest (most keys) 64-query tiles first (as _prefill_meta)
-            items += [(-(s.start_pos + min(n, (t + 1) * PREFILL_TILE)), i, t)
-                      for t in range(math.ceil(n / PREFILL_TILE))]
+            items += [(-(s.start_pos + min(n, (t + 1) * self.tile)), i, t)
+                      for t in range(math.ceil(n / self.tile))]
             row += n
         items.sort()
         ws[:] = self.ns  # padded items -> the empty sequence

@@ -43,6 +43,10 @@ class LayerWeights:
     wo_t: torch.Tensor = None
     wgu_t: torch.Tensor = None
     wd_t: torch.Tensor = None
+    # per-layer dequantisation scales of an fp8 KV cache (stored = x / scale); 1.0 unless the checkpoint carries
+    # vLLM's model.layers.N.self_attn.k_scale / .v_scale.  The same on every TP rank.  Unused with a bf16 cache.
+    k_scale: float = 1.0
+    v_scale: float = 1.0
 
 
 @dataclass
@@ -105,6 +109,16 @@ def _permute_units(w: torch.Tensor) -> torch.Tensor:
     return w.view(units, 128, -1)[:, perm, :].reshape(w.shape)
 
 
+def _kv_scale(t) -> float:
+    """An optional checkpoint scale tensor (one element) as a positive finite float; absent = 1.0."""
+    if t is None:
+        return 1.0
+    v = float(torch.as_tensor(t).float().reshape(-1)[0])
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"KV cache scale must be positive and finite, got {v}")
+    return v
+
+
 def convert_standard(cfg: MistralConfig, std, tp_rank: int = 0, tp_size: int = 1, device="cpu") -> EngineWeights:
     """Standard (HF-layout) weights -> this rank's engine weights."""
     cfg.validate(tp_size)
@@ -126,7 +140,8 @@ def convert_standard(cfg: MistralConfig, std, tp_rank: int = 0, tp_size: int = 1
         layers.append(LayerWeights(
             attn_norm=L["attn_norm"].contiguous().to(device), wqkv=wqkv.contiguous().to(device),
             wo=wo.contiguous().to(device), ffn_norm=L["ffn_norm"].contiguous().to(device),
-            wgu=wgu.contiguous().to(device), wd=wd.contiguous().to(device)))
+            wgu=wgu.contiguous().to(device), wd=wd.contiguous().to(device),
+            k_scale=_kv_scale(L.get("k_scale")), v_scale=_kv_scale(L.get("v_scale"))))
     return attach_tiled(EngineWeights(
         cfg=cfg, tp_rank=tp_rank, tp_size=tp_size, embed=std["embed"].contiguous().to(device), layers=layers,
         final_norm=std["final_norm"].contiguous().to(device), lm_head=std["lm_head"][r * V:(r + 1) * V].contiguous().to(device)))
@@ -191,5 +206,6 @@ def load_safetensors(cfg: MistralConfig, path: str, tp_rank: int = 0, tp_size: i
             "ffn_norm": tensors[p + "post_attention_layernorm.weight"],
             "gate": tensors[p + "mlp.gate_proj.weight"], "up": tensors[p + "mlp.up_proj.weight"],
             "down": tensors[p + "mlp.down_proj.weight"],
+            "k_scale": tensors.get(p + "self_attn.k_scale"), "v_scale": tensors.get(p + "self_attn.v_scale"),
         })
     return convert_standard(cfg, std, tp_rank, tp_size, device)

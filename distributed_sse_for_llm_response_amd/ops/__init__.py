@@ -85,12 +85,16 @@ def gemm_silu(x, w, out):
         ref.gemm_silu(x, w, out)
 
 
-def gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv):
-    """Fused QKV projection + RoPE + paged KV write (decode)."""
+def gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0,
+                  scratch=None):
+    """Fused QKV projection + RoPE + paged KV write (decode).  The cache tensors' dtype selects the kernels: bf16, or
+    float8_e4m3fn with the layer's k_scale / v_scale (stored = x / scale; ops/reference.py quantize_kv).  scratch
+    (fp8 on the GPU only): an fp32 buffer of at least M x N floats for the projection's sums, else one is allocated."""
     if _hip(x):
-        torch.ops.dsse.gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv)
+        torch.ops.dsse.gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale,
+                                     scratch)
     else:
-        ref.gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv)
+        ref.gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
 
 
 def gemm_resid_split(x, w, resid, part) -> int:
@@ -142,11 +146,11 @@ def rmsnorm(resid, w, y, eps, delta=None, embed=None, ids=None, part=None, nspli
         ref.rmsnorm(resid, w, y, eps, delta, embed, ids, part, nsplit)
 
 
-def rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv):
+def rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
     if _hip(qkv):
-        torch.ops.dsse.rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv)
+        torch.ops.dsse.rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
     else:
-        ref.rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv)
+        ref.rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
 
 
 def silu_mul(gu, h):
@@ -171,15 +175,16 @@ def ring_advance(counter):
 
 
 def paged_attention(mode, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq, work_tile, out,
-                    part_o, part_ml, part, nparts):
+                    part_o, part_ml, part, nparts, k_scale=1.0, v_scale=1.0):
     """mode 0 = decode (flash-decoding partitions), 1 = prefill on 16-query tiles (decode-style kernel),
-    2 = flash prefill on 64-query tiles (LDS-staged K/V, attention_prefill.hip)."""
+    2 = flash prefill on 64-query tiles (LDS-staged K/V, attention_prefill.hip).  A float8_e4m3fn cache (modes 0 and
+    1; the flash kernel has no fp8 form and the HIP op refuses it) is read as stored * scale."""
     if _hip(q):
         torch.ops.dsse.paged_attention(mode, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq,
-                                       work_tile, out, part_o, part_ml, part, nparts)
+                                       work_tile, out, part_o, part_ml, part, nparts, k_scale, v_scale)
     else:
         ref.paged_attention(mode, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq, work_tile,
-                            out, part_o, part_ml, part, nparts)
+                            out, part_o, part_ml, part, nparts, k_scale, v_scale)
 
 
 def flash_prefill_split(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work, comb, out, part_o, part_ml,
@@ -191,24 +196,27 @@ def flash_prefill_split(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_l
         torch.ops.dsse.flash_prefill_split(q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work, comb, out,
                                            part_o, part_ml, nslots)
     else:  # the split is a schedule: the reference computes each tile whole (a split tile's items repeat it)
+        if ref.is_fp8(k_cache):
+            raise TypeError("flash_prefill_split has no float8_e4m3fn KV cache form: use paged_attention mode 1")
         nw = work.numel() // 5
         ref.paged_attention(2, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work[:nw], work[nw:2 * nw],
                             out, part_o, part_ml, 32, 1)
 
 
 def qkv_attention_decode(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, slabs, block_tables, q_start,
-                         q_len, ctx_len, work_seq, work_tile, out, part_o, part_ml, part, nparts) -> int:
+                         q_len, ctx_len, work_seq, work_tile, out, part_o, part_ml, part, nparts, k_scale=1.0,
+                         v_scale=1.0) -> int:
     """Decode QKV projection + RoPE + KV write + attention.  HIP: the GEMM leaves fp32 split-K slabs in `slabs`
     and the attention kernel folds the reduction, RoPE and the K/V write in (returns the slab count; 0 = it ran
     gemm_qkv_rope + paged_attention instead).  Same result as those two ops."""
     if _hip(x):
         return int(torch.ops.dsse.qkv_attention_decode(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv,
                                                        slabs, block_tables, q_start, q_len, ctx_len, work_seq,
-                                                       work_tile, out, part_o, part_ml, part, nparts))
+                                                       work_tile, out, part_o, part_ml, part, nparts, k_scale, v_scale))
     B = x.shape[0]
-    ref.gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv)
+    ref.gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
     ref.paged_attention(0, q_out.view(B, nh, 128), k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq,
-                        work_tile, out.view(B, nh, 128), part_o, part_ml, part, nparts)
+                        work_tile, out.view(B, nh, 128), part_o, part_ml, part, nparts, k_scale, v_scale)
     return 0
 
 

@@ -86,15 +86,43 @@ def _rope(x: torch.Tensor, positions: torch.Tensor, rope: torch.Tensor) -> torch
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
 
 
-def _write_kv(k: torch.Tensor, v: torch.Tensor, slots: torch.Tensor, k_cache, v_cache):
+# ---- FP8 (e4m3fn) KV cache: the one definition of what a cache byte holds --------------------------------------
+# Stored value = x / scale, per-layer fp32 scalars k_scale / v_scale; used value = stored * scale.  Quantisation is
+# clamp(x * (1 / scale), -448, 448) in fp32, then ONE round-to-nearest-even to e4m3fn, taken from the fp32 value
+# (the rotated K, the summed V) -- never from a bf16 copy of it.  The clamp is explicit: torch's own cast gives NaN
+# above 464.  A key or value enters attention only as its dequantised cache value.
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def is_fp8(cache: torch.Tensor) -> bool:
+    return cache.dtype == FP8
+
+
+def quantize_kv(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """fp32 values -> e4m3fn cache elements (x / scale, clamped to +-448, rounded once)."""
+    inv = torch.tensor(1.0 / float(scale), dtype=torch.float32, device=x.device)  # 1 / scale rounded to fp32, as the kernels get it
+    return (x.float() * inv).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def dequantize_kv(c: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """Cache elements -> the fp32 values attention uses (bf16 cache: the values themselves)."""
+    return c.float() * float(scale) if is_fp8(c) else c.float()
+
+
+def _to_cache(x: torch.Tensor, cache: torch.Tensor, scale: float) -> torch.Tensor:
+    return quantize_kv(x, scale) if is_fp8(cache) else x.to(cache.dtype)
+
+
+def _write_kv(k: torch.Tensor, v: torch.Tensor, slots: torch.Tensor, k_cache, v_cache, k_scale=1.0, v_scale=1.0):
     """k, v: [M, Hkv, 128] (natural order) -> paged caches at `slots` (skip slot < 0)."""
     for m in range(k.shape[0]):
         s = int(slots[m])
         if s < 0:
             continue
         blk, off = s // PAGE, s % PAGE
-        k_cache[blk, :, off, :] = k[m].to(k_cache.dtype)
-        v_cache[blk, :, :, int(vperm(torch.tensor(off)))] = v[m].to(v_cache.dtype)
+        k_cache[blk, :, off, :] = _to_cache(k[m], k_cache, k_scale)
+        v_cache[blk, :, :, int(vperm(torch.tensor(off)))] = _to_cache(v[m], v_cache, v_scale)
 
 
 # ---------------------------------------------------------------- GEMMs
@@ -113,21 +141,21 @@ def gemm_silu(x, w, out):
     out.copy_((torch.nn.functional.silu(g) * u).reshape(x.shape[0], -1).to(out.dtype))
 
 
-def gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv):
+def gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
     M = x.shape[0]
     y = x.float() @ untile_weight(w).float().t()
     qkv = _unpermute_units(y, nh + 2 * nkv)
     rot = _rope(qkv[:, : nh + nkv], positions[:M], rope)
     q_out.view(-1)[: M * nh * HEAD_DIM].copy_(rot[:, :nh].reshape(-1).to(q_out.dtype))
-    _write_kv(rot[:, nh:], qkv[:, nh + nkv:], slots[:M], k_cache, v_cache)
+    _write_kv(rot[:, nh:], qkv[:, nh + nkv:], slots[:M], k_cache, v_cache, k_scale, v_scale)
 
 
-def rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv):
+def rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
     T = qkv.shape[0]
     u = _unpermute_units(qkv.float(), nh + 2 * nkv)
     rot = _rope(u[:, : nh + nkv], positions[:T], rope)
     q_out.view(-1)[: T * nh * HEAD_DIM].copy_(rot[:, :nh].reshape(-1).to(q_out.dtype))
-    _write_kv(rot[:, nh:], u[:, nh + nkv:], slots[:T], k_cache, v_cache)
+    _write_kv(rot[:, nh:], u[:, nh + nkv:], slots[:T], k_cache, v_cache, k_scale, v_scale)
 
 
 def silu_mul(gu, h):
@@ -168,19 +196,23 @@ def ring_advance(counter):
 
 
 # ---------------------------------------------------------------- attention
-def gather_kv(k_cache, v_cache, block_table, n):
-    """Keys/values 0..n-1 of one sequence in natural order: ([n, Hkv, 128], [n, Hkv, 128])."""
+def gather_kv(k_cache, v_cache, block_table, n, k_scale=1.0, v_scale=1.0):
+    """Keys/values 0..n-1 of one sequence in natural order: ([n, Hkv, 128], [n, Hkv, 128]); an fp8 cache is
+    dequantised (stored * scale)."""
     ks, vs = [], []
     pos_of_tok = vperm(torch.arange(PAGE)).to(v_cache.device)  # natural token t lives at pos_of_tok[t]
     for p in range((n + PAGE - 1) // PAGE):
         blk = int(block_table[p])
         ks.append(k_cache[blk].permute(1, 0, 2).float())               # [32, Hkv, 128]
         vs.append(v_cache[blk][:, :, pos_of_tok].permute(2, 0, 1).float())  # [32, Hkv, 128]
-    return torch.cat(ks)[:n], torch.cat(vs)[:n]
+    K, V = torch.cat(ks)[:n], torch.cat(vs)[:n]
+    if is_fp8(k_cache):
+        K, V = K * float(k_scale), V * float(v_scale)
+    return K, V
 
 
 def paged_attention(mode, q, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq, work_tile,
-                    out, part_o=None, part_ml=None, part=0, nparts=1):
+                    out, part_o=None, part_ml=None, part=0, nparts=1, k_scale=1.0, v_scale=1.0):
     """Causal GQA attention of each sequence's queries over its paged keys (all work items)."""
     hq, hkv = q.shape[1], k_cache.shape[1]
     G = hq // hkv
@@ -190,7 +222,7 @@ def paged_attention(mode, q, k_cache, v_cache, block_tables, q_start, q_len, ctx
         if ql <= 0:
             continue
         qs = int(q_start[b])
-        K, V = gather_kv(k_cache, v_cache, block_tables[b], ctx)
+        K, V = gather_kv(k_cache, v_cache, block_tables[b], ctx, k_scale, v_scale)
         K = K.repeat_interleave(G, dim=1)  # [ctx, hq, 128]
         V = V.repeat_interleave(G, dim=1)
         Q = q[qs: qs + ql].float()          # [ql, hq, 128]

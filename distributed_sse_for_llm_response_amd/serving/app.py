@@ -22,7 +22,7 @@ import torch
 
 from .. import runtime as rt_mod
 from ..engine.engine import FINISH_CODES, EngineFault, LLMEngine, SamplingParams, TokenEvent
-from ..engine.kv_cache import KVCache
+from ..engine.kv_cache import KVCache, kv_cache_torch_dtype
 from ..engine.model_runner import ModelRunner
 from ..models.mistral import TINY, get_config, init_standard_weights
 from ..models.tokenizer import get_tokenizer, prompt_for_request
@@ -40,7 +40,8 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         tp_rank, tp = (comm.rank, comm.size) if comm is not None else (0, 1)
         w = convert_standard(mcfg, init_standard_weights(mcfg, seed=cfg.seed), tp_rank=tp_rank, tp_size=tp)
         runner = ModelRunner(w, num_blocks=256, max_batch=min(cfg.max_batch, 8),
-                             max_model_len=min(cfg.max_model_len, 1024), device="cpu", comm=comm, use_graphs=False)
+                             max_model_len=min(cfg.max_model_len, 1024), device="cpu", comm=comm, use_graphs=False,
+                             kv_cache_dtype=cfg.kv_cache_dtype)
     else:
         device = device or torch.device("cuda", torch.cuda.current_device())
         mcfg = get_config(cfg.model)
@@ -52,11 +53,17 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         free, total = torch.cuda.mem_get_info(device)
         budget = int(total * cfg.gpu_memory_utilization) - (total - free) - (2 << 30)
         nkv = mcfg.num_kv_heads // tp
-        nblk = max(64, min(KVCache.blocks_for_budget(budget, mcfg.num_layers, nkv),
+        nblk = max(64, min(KVCache.blocks_for_budget(budget, mcfg.num_layers, nkv, kv_cache_torch_dtype(cfg.kv_cache_dtype)),
                            cfg.max_batch * (cfg.max_model_len // 32 + 2) * 4))
         runner = ModelRunner(w, num_blocks=nblk, max_batch=cfg.max_batch, max_model_len=cfg.max_model_len,
-                             device=device, comm=comm)
+                             device=device, comm=comm, kv_cache_dtype=cfg.kv_cache_dtype)
         runner.capture()
+    kv = runner.kv
+    if comm is None or comm.rank == 0:
+        print(f"[engine] KV cache: {'fp8_e4m3' if kv.is_fp8 else 'bf16'} ({cfg.kv_cache_dtype}), "
+              f"{KVCache.bytes_per_block(kv.num_layers, kv.nkv, kv.dtype) // 32 // 1024} KiB per token"
+              f"{' per rank' if comm is not None and comm.size > 1 else ''}, {kv.num_blocks} pages of 32 tokens",
+              flush=True)
     tok = get_tokenizer(mcfg.vocab_size, cfg.tokenizer_path or None)
     runner.set_guide_vocab(tok.pieces(), tok.eos_id)  # guided decoding constrains the text: the pieces' bytes
     engine = LLMEngine(runner, eos_id=tok.eos_id, prefill_budget=cfg.prefill_budget, max_pause_s=cfg.max_pause_s,

@@ -10,13 +10,25 @@ Flow control (new): FLOW_HIGH_WATER (bytes queued for every subscriber of a conv
   pauses; 0 = off), MAX_PAUSE_S (a paused stream resumes after this long regardless).
 Engine keys (new): TP, DP, DP_PREFIX, DP_WORKER_TIMEOUT_MS, MAX_MODEL_LEN, MAX_BATCH, KV_BLOCK (fixed 32), GPU_MEMORY_UTILIZATION,
   SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH, ENABLE_PREFIX_CACHING (default 0),
-  DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured).
+  DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured), KV_CACHE_DTYPE (auto | bf16 | fp8 | fp8_e4m3; default auto = bf16).
 """
 from __future__ import annotations
 
 import argparse
 import os
 from dataclasses import asdict, dataclass, fields
+
+
+# the one list of KV cache element types (engine/kv_cache.py imports it; kept here: no torch import at parse time)
+KV_CACHE_DTYPES = ("auto", "bf16", "fp8", "fp8_e4m3")
+
+
+def parse_kv_cache_dtype(v) -> str:
+    """The option as typed (lower-cased); a value outside the choices is a start-up error that names them."""
+    key = str(v).strip().lower()
+    if key not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype / KV_CACHE_DTYPE must be one of {', '.join(KV_CACHE_DTYPES)}; got {v!r}")
+    return key
 
 
 def _env(name, default, cast=str):
@@ -75,6 +87,9 @@ class ServeConfig:
     # DP router: a chat's affine replica wins while its outstanding count is at most the least one plus this slack
     # (only with prefix caching on; the default is a guess nobody has measured)
     dp_prefix_affinity_slack: int = 4
+    # KV cache element type: auto = bf16 (128 KiB per token at TP = 1), fp8 = fp8_e4m3 (64 KiB per token, twice the
+    # pages in the same budget); passed to every engine replica / TP rank
+    kv_cache_dtype: str = "auto"
 
     @classmethod
     def from_env(cls) -> "ServeConfig":
@@ -119,6 +134,7 @@ class ServeConfig:
         c.dp_worker_timeout_ms = _env("DP_WORKER_TIMEOUT_MS", c.dp_worker_timeout_ms, int)
         c.enable_prefix_caching = _env("ENABLE_PREFIX_CACHING", c.enable_prefix_caching, bool)
         c.dp_prefix_affinity_slack = _env("DP_PREFIX_AFFINITY_SLACK", c.dp_prefix_affinity_slack, int)
+        c.kv_cache_dtype = _env("KV_CACHE_DTYPE", c.kv_cache_dtype, parse_kv_cache_dtype)
         return c
 
     @classmethod
@@ -126,6 +142,9 @@ class ServeConfig:
         for f in fields(cls):
             if isinstance(f.default, bool):  # a switch: --enable-prefix-caching
                 ap.add_argument("--" + f.name.replace("_", "-"), action="store_const", const=True, default=None)
+                continue
+            if f.name == "kv_cache_dtype":  # --help lists the choices; a bad value is a usage error that names them
+                ap.add_argument("--kv-cache-dtype", type=str.lower, choices=KV_CACHE_DTYPES, default=None)
                 continue
             ap.add_argument("--" + f.name.replace("_", "-"), type=type(f.default) if f.default is not None else str,
                             default=None)
@@ -135,6 +154,7 @@ class ServeConfig:
             v = getattr(ns, f.name, None)
             if v is not None:
                 setattr(self, f.name, v)
+        self.kv_cache_dtype = parse_kv_cache_dtype(self.kv_cache_dtype)
         return self
 
     def to_json(self) -> str:

@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--configs", default="KWV=4;KWV=1")
     ap.add_argument("--target-wgs", default="512", help="flash-decoding partition targets to sweep")
     ap.add_argument("--seq-pages", action="store_true", help="pages in cache order instead of a random permutation")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"], help="KV cache element type (fp8 = e4m3)")
     args = ap.parse_args()
     ops.load_library(required=True)
     base_cfg = os.environ.get("DSSE_KERNEL_CFG", "")
@@ -38,10 +39,12 @@ def main():
         for ctx in [int(c) for c in args.ctx.split(",")]:
             npg = math.ceil(ctx / 32)
             total = B * npg
-            kv_bytes = B * ctx * args.hkv * 128 * 2 * 2
+            f8 = args.kv_dtype == "fp8"
+            kv_bytes = B * ctx * args.hkv * 128 * 2 * (1 if f8 else 2)
             copies = max(2, (600 << 20) // max(1, kv_bytes) + 1)
-            ks = [torch.randn(total, args.hkv, 32, 128, device=dev, dtype=torch.bfloat16) for _ in range(copies)]
-            vs = [torch.randn(total, args.hkv, 128, 32, device=dev, dtype=torch.bfloat16) for _ in range(copies)]
+            kvt = torch.float8_e4m3fn if f8 else torch.bfloat16
+            ks = [torch.randn(total, args.hkv, 32, 128, device=dev, dtype=torch.bfloat16).to(kvt) for _ in range(copies)]
+            vs = [torch.randn(total, args.hkv, 128, 32, device=dev, dtype=torch.bfloat16).to(kvt) for _ in range(copies)]
             order = torch.arange(total, device=dev) if args.seq_pages else torch.randperm(total, device=dev)
             bt = order.to(torch.int32).view(B, npg)
             bt = torch.cat([bt, torch.zeros(B, 1, device=dev, dtype=torch.int32)], 1).contiguous()
@@ -80,7 +83,7 @@ def main():
                 en.record()
                 torch.cuda.synchronize()
                 us = st.elapsed_time(en) / args.iters * 1e3
-                print(f"B={B:4d} ctx={ctx:5d} nparts={nparts:2d} cfg={cfg:16s} {us:8.2f} us  "
+                print(f"kv={args.kv_dtype} B={B:4d} ctx={ctx:5d} nparts={nparts:2d} cfg={cfg:16s} {us:8.2f} us  "
                       f"{kv_bytes / us / 1e6:6.3f} TB/s", flush=True)
             del ks, vs
             torch.cuda.empty_cache()

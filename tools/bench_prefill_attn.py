@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--sdpa", action="store_true")
     ap.add_argument("--mode1", default="", help="comma list of key partition counts for mode-1 arms")
     ap.add_argument("--eager", action="store_true", help="time eager back-to-back calls instead of a graph")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="KV cache element type; fp8 (e4m3) has no flash form: only the --mode1 arms run")
     args = ap.parse_args()
     ops.load_library(required=True)
     dev = torch.device("cuda", 0)
@@ -41,8 +43,9 @@ def main():
     res = {}
     for T in [int(t) for t in args.T.split(",")]:
         npg = math.ceil(T / PAGE)
-        k_cache = torch.randn(npg, args.hkv, PAGE, 128, device=dev, dtype=torch.bfloat16)
-        v_cache = torch.randn(npg, args.hkv, 128, PAGE, device=dev, dtype=torch.bfloat16)
+        kvt = torch.float8_e4m3fn if args.kv_dtype == "fp8" else torch.bfloat16
+        k_cache = torch.randn(npg, args.hkv, PAGE, 128, device=dev, dtype=torch.bfloat16).to(kvt)
+        v_cache = torch.randn(npg, args.hkv, 128, PAGE, device=dev, dtype=torch.bfloat16).to(kvt)
         bt = torch.randperm(npg, device=dev).to(torch.int32).view(1, npg)
         q = torch.randn(T, args.hq, 128, device=dev, dtype=torch.bfloat16)
         out = torch.empty_like(q)
@@ -57,7 +60,7 @@ def main():
             ops.paged_attention(2, q, k_cache, v_cache, bt, q_start, q_len, ctx_len, work_seq, work_tile, out,
                                 dummy, dummy, 32 * math.ceil((T + 31) / 32), 1)
 
-        arms = {"flash": flash}
+        arms = {"flash": flash} if args.kv_dtype == "bf16" else {}
         # --mode1 N,...: the decode-style kernel on 64-query work items (4 tiles of 16) with the keys in N partitions
         # merged by the combine kernel (paged_attention mode 1): more workgroups for short prompts
         # (a mode-1 work item is 4 tiles of 16 / G queries: 16 queries of all G heads at G = 4)
@@ -69,6 +72,10 @@ def main():
             pml = torch.empty(n1 * args.hkv * npart * 64 * 2, device=dev)
             arms[f"m1p{npart}"] = (lambda po=po, pml=pml, part=part, npart=npart: ops.paged_attention(
                 1, q, k_cache, v_cache, bt, q_start, q_len, ctx_len, ws1, wt1, out, po, pml, part, npart))
+        if args.kv_dtype == "fp8":
+            if not arms:
+                raise SystemExit("--kv-dtype fp8 runs the paged prefill kernel only: give --mode1 1 (or more partitions)")
+            flash = next(iter(arms.values()))  # the arm the determinism screen below repeats
         if args.sdpa:
             # contiguous [1, H, T, d] copies of the same K/V (GQA expanded), causal
             kk = k_cache[bt[0].long()].permute(1, 0, 2, 3).reshape(args.hkv, T, 128)

@@ -47,7 +47,7 @@ def cached_prefix_main(args):
     w = random_engine_weights(cfg, device=device, seed=7)
     max_len = n + 4 * PAGE
     r = ModelRunner(w, num_blocks=4 * blocks_needed(max_len) + 4, max_batch=2, max_model_len=max_len, device=device,
-                    max_prefill_tokens=max(args.chunk, 8192))
+                    max_prefill_tokens=max(args.chunk, 8192), kv_cache_dtype=args.kv_dtype)
     r.capture()
     engines = {on: LLMEngine(r, eos_id=-1, prefill_budget=r.max_prefill_tokens, prefix_cache=on) for on in (False, True)}
     gen = torch.Generator().manual_seed(5)
@@ -97,6 +97,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=8192)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--decode-steps", type=int, default=16)
+    ap.add_argument("--kv-dtype", default="auto", choices=["auto", "bf16", "fp8", "fp8_e4m3"],
+                    help="KV cache element type (fp8: prompts attend on the paged prefill kernel, not the flash kernel)")
     ap.add_argument("--profile-marker", action="store_true",
                     help="launch one bitwise_not kernel after the warm-up iteration: tools/trace_sum.py --after-kernel "
                          "bitwise_not then keeps only the timed iterations of a rocprofv3 kernel trace")
@@ -129,7 +131,7 @@ def main():
     per = blocks_needed(max_len)
     B = max(1, args.prompts)
     r = ModelRunner(w, num_blocks=B * per + 4, max_batch=B, max_model_len=max_len, device=device, comm=comm,
-                    max_prefill_tokens=max(args.chunk, 8192))
+                    max_prefill_tokens=max(args.chunk, 8192), kv_cache_dtype=args.kv_dtype)
     r.capture([B])
     gen = torch.Generator().manual_seed(5)
 
