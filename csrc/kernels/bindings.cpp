@@ -1033,9 +1033,45 @@ int64_t qkv_attention_decode(const Tensor& x, const Tensor& w, const Tensor& pos
   return S;
 }
 
+// ---- operand checks shared by the sampler ops ------------------------------------------------------------------
+// Rows: `active` int32 [>= B] or none (every row runs); row b is slot row_slot[b], or slot b without the map (then
+// B <= slots).  One template over SampleParams / LogprobParams / GuideParams: all three name the fields alike.
+template <class P>
+void bind_rows(P& p, const c10::optional<Tensor>& active, const c10::optional<Tensor>& row_slot, int B, int slots) {
+  if (active.has_value()) {
+    check_gpu(*active, "active");
+    check_dtype(*active, at::kInt, "active");
+    TORCH_CHECK(active->numel() >= B, "active too short");
+    p.active = active->data_ptr<int>();
+  }
+  if (row_slot.has_value()) {
+    check_gpu(*row_slot, "row_slot");
+    check_dtype(*row_slot, at::kInt, "row_slot");
+    TORCH_CHECK(row_slot->numel() >= B, "row_slot too short");
+    p.row_slot = row_slot->data_ptr<int>();
+  } else {
+    TORCH_CHECK(B <= slots, "more rows than slots (no row_slot map)");
+  }
+}
+
+// Logits [B, V] fp32 of the passes that take a row stride (rows may be strided: a column slice of a shard): sets
+// p.ld / p.V / p.vocab_offset and returns the data pointer.
+template <class P>
+float* bind_logits(P& p, const Tensor& logits, int64_t vocab_offset) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");
+  check_dtype(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
+                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= 32768, "sampler supports V <= 32768 per rank");
+  TORCH_CHECK(vocab_offset >= 0 && vocab_offset <= INT32_MAX - 32768, "vocab_offset out of range");
+  p.ld = (int)logits.stride(0);
+  p.V = (int)logits.size(1);
+  p.vocab_offset = (int)vocab_offset;
+  return logits.data_ptr<float>();
+}
+
 dsse::SampleParams sample_params(const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
-                                 const Tensor& seeds, const Tensor& positions,
-                                 const c10::optional<Tensor>& active, int B) {
+                                 const Tensor& seeds, const Tensor& positions, int B) {
   for (const Tensor* t : {&temperature, &top_k, &top_p, &seeds, &positions}) check_gpu(*t, "sampling metadata");
   check_dtype(temperature, at::kFloat, "temperature");
   check_dtype(top_k, at::kInt, "top_k");
@@ -1050,68 +1086,7 @@ dsse::SampleParams sample_params(const Tensor& temperature, const Tensor& top_k,
   p.top_p = top_p.data_ptr<float>();
   p.seeds = reinterpret_cast<const uint2*>(seeds.data_ptr<int>());
   p.positions = positions.data_ptr<int>();
-  if (active.has_value()) {
-    check_gpu(*active, "active");
-    check_dtype(*active, at::kInt, "active");
-    TORCH_CHECK(active->numel() >= B, "active too short");
-    p.active = active->data_ptr<int>();
-  }
   return p;
-}
-
-// Per-rank candidate pass: cand [B, nchunks, 2] fp32 (score, index bits).
-void sample_candidates(const Tensor& logits, const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
-                       const Tensor& seeds, const Tensor& positions, const c10::optional<Tensor>& active,
-                       Tensor& cand, int64_t vocab_offset) {
-  check_gpu(logits, "logits");
-  check_dtype(logits, at::kFloat, "logits");
-  check_gpu(cand, "cand");
-  check_dtype(cand, at::kFloat, "cand");
-  const int B = (int)logits.size(0), V = (int)logits.size(1);
-  TORCH_CHECK(V <= 32768, "sampler supports V <= 32768 per rank");
-  TORCH_CHECK(cand.dim() == 3 && cand.size(0) == B && cand.size(2) == 2, "cand must be [B, nchunks, 2]");
-  dsse::SampleParams p = sample_params(temperature, top_k, top_p, seeds, positions, active, B);
-  p.logits = logits.data_ptr<float>();
-  p.ld = V;
-  p.V = V;
-  p.vocab_offset = (int)vocab_offset;
-  p.cand = reinterpret_cast<float2*>(cand.data_ptr<float>());
-  p.nchunks = (int)cand.size(1);
-  DSSE_CHECK_HIP(dsse_sample(B, &p, cur_stream()));
-}
-
-// Merge pass over cand_all [world, B, nchunks, 2] and commit: next_ids, ring[head], positions += 1.
-void sample_pick(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
-                 const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
-                 const c10::optional<Tensor>& positions_inc, int64_t vocab) {
-  check_gpu(cand_all, "cand_all");
-  check_gpu(next_ids, "next_ids");
-  check_dtype(next_ids, at::kInt, "next_ids");
-  TORCH_CHECK(cand_all.dim() == 4 && cand_all.size(3) == 2, "cand_all must be [world, B, nchunks, 2]");
-  const int world = (int)cand_all.size(0), B = (int)cand_all.size(1);
-  TORCH_CHECK(next_ids.numel() >= B, "next_ids too short");
-  dsse::SampleParams p{};
-  p.nchunks = (int)cand_all.size(2);
-  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
-  p.next_ids = next_ids.data_ptr<int>();
-  if (active.has_value()) {
-    TORCH_CHECK(active->numel() >= B, "active too short");
-    p.active = active->data_ptr<int>();
-  }
-  if (ring.has_value()) {
-    TORCH_CHECK(ring_counter.has_value(), "ring needs ring_counter");
-    check_gpu(*ring, "ring");
-    TORCH_CHECK(ring->dim() == 2 && ring->size(1) >= B, "ring must be [R, >= B]");
-    p.ring = ring->data_ptr<int>();
-    p.ring_counter = ring_counter->data_ptr<int>();
-    p.ring_size = (int)ring->size(0);
-    p.ring_stride = (int)ring->size(1);
-  }
-  if (positions_inc.has_value()) {
-    TORCH_CHECK(positions_inc->numel() >= B, "positions_inc too short");
-    p.positions_inc = positions_inc->data_ptr<int>();
-  }
-  DSSE_CHECK_HIP(dsse_sample_pick(B, world, cand_all.data_ptr(), &p, cur_stream()));
 }
 
 // ---- presence / frequency / repetition penalties (sampler.hip sample_penalty_kernel, hist_append) ----------------
@@ -1131,41 +1106,16 @@ void penalty_state(dsse::SampleParams& p, const Tensor& pen_meta, const Tensor& 
   p.pen_slots = (int)hist.size(0);
 }
 
-void penalty_rows(dsse::SampleParams& p, const c10::optional<Tensor>& active, const c10::optional<Tensor>& row_slot,
-                  int B) {
-  if (active.has_value()) {
-    check_gpu(*active, "active");
-    check_dtype(*active, at::kInt, "active");
-    TORCH_CHECK(active->numel() >= B, "active too short");
-    p.active = active->data_ptr<int>();
-  }
-  if (row_slot.has_value()) {
-    check_gpu(*row_slot, "row_slot");
-    check_dtype(*row_slot, at::kInt, "row_slot");
-    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
-    p.row_slot = row_slot->data_ptr<int>();
-  } else {
-    TORCH_CHECK(B <= p.pen_slots, "more rows than slots (no row_slot map)");
-  }
-}
-
 // In place on logits [B, V] (row stride >= V), before sample_candidates.
 void sample_penalties(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& pen_meta, const Tensor& hist,
                       const c10::optional<Tensor>& row_slot, int64_t vocab_offset, int64_t vocab) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");  // (rows may be strided: a column slice of a shard)
-  check_dtype(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
-                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
-  const int B = (int)logits.size(0), V = (int)logits.size(1);
-  TORCH_CHECK(V >= 1 && V <= 32768, "sampler supports V <= 32768 per rank");
   dsse::SampleParams p{};
+  float* x = bind_logits(p, logits, vocab_offset);
+  const int B = (int)logits.size(0);
   penalty_state(p, pen_meta, hist);
-  penalty_rows(p, active, row_slot, B);
-  p.ld = (int)logits.stride(0);
-  p.V = V;
-  p.vocab_offset = (int)vocab_offset;
+  bind_rows(p, active, row_slot, B, p.pen_slots);
   p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
-  DSSE_CHECK_HIP(dsse_sample_penalties(B, logits.data_ptr<float>(), &p, cur_stream()));
+  DSSE_CHECK_HIP(dsse_sample_penalties(B, x, &p, cur_stream()));
 }
 
 // ---- logit_bias / min_tokens / stop_token_ids and min_p (sampler.hip sample_bias_ban_kernel, row_min_p) -----------
@@ -1188,53 +1138,30 @@ void control_state(dsse::SampleParams& p, const Tensor& ctl_meta, const c10::opt
   }
 }
 
-void control_rows(dsse::SampleParams& p, const c10::optional<Tensor>& row_slot, int B) {
-  if (row_slot.has_value()) {
-    check_gpu(*row_slot, "row_slot");
-    check_dtype(*row_slot, at::kInt, "row_slot");
-    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
-    p.row_slot = row_slot->data_ptr<int>();
-  } else {
-    TORCH_CHECK(B <= p.ctl_slots, "more rows than slots (no row_slot map)");
-  }
-}
-
 // In place on logits [B, V] (row stride >= V): after logprob_stats, before sample_penalties.  positions [B] = the
 // position of each row's predecessor token (what sample_candidates takes).
 void sample_bias_ban(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& ctl_meta,
                      const Tensor& ctl_body, const Tensor& positions, const c10::optional<Tensor>& row_slot,
                      int64_t vocab_offset, int64_t vocab) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");
-  check_dtype(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
-                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
-  const int B = (int)logits.size(0), V = (int)logits.size(1);
-  TORCH_CHECK(V >= 1 && V <= 32768, "sampler supports V <= 32768 per rank");
+  dsse::SampleParams p{};
+  float* x = bind_logits(p, logits, vocab_offset);
+  const int B = (int)logits.size(0);
   check_gpu(positions, "positions");
   check_dtype(positions, at::kInt, "positions");
   TORCH_CHECK(positions.numel() >= B, "positions too short");
-  dsse::SampleParams p{};
   control_state(p, ctl_meta, ctl_body);
-  control_rows(p, row_slot, B);
-  if (active.has_value()) {
-    check_gpu(*active, "active");
-    check_dtype(*active, at::kInt, "active");
-    TORCH_CHECK(active->numel() >= B, "active too short");
-    p.active = active->data_ptr<int>();
-  }
+  bind_rows(p, active, row_slot, B, p.ctl_slots);
   p.positions = positions.data_ptr<int>();
-  p.ld = (int)logits.stride(0);
-  p.V = V;
-  p.vocab_offset = (int)vocab_offset;
   p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
-  DSSE_CHECK_HIP(dsse_sample_bias_ban(B, logits.data_ptr<float>(), &p, cur_stream()));
+  DSSE_CHECK_HIP(dsse_sample_bias_ban(B, x, &p, cur_stream()));
 }
 
-// sample_candidates with min_p: ctl_meta's fourth column holds min_p per slot (row b = slot row_slot[b], else b).
-void sample_candidates_min_p(const Tensor& logits, const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
-                             const Tensor& seeds, const Tensor& positions, const c10::optional<Tensor>& active,
-                             Tensor& cand, const Tensor& ctl_meta, const c10::optional<Tensor>& row_slot,
-                             int64_t vocab_offset) {
+// Per-rank candidate pass: cand [B, nchunks, 2] fp32 (score, index bits).  With ctl_meta: min_p, its fourth column,
+// per slot (row b = slot row_slot[b], else b).
+void sample_candidates_impl(const Tensor& logits, const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
+                            const Tensor& seeds, const Tensor& positions, const c10::optional<Tensor>& active,
+                            Tensor& cand, const Tensor* ctl_meta, const c10::optional<Tensor>& row_slot,
+                            int64_t vocab_offset) {
   check_gpu(logits, "logits");
   check_dtype(logits, at::kFloat, "logits");
   check_gpu(cand, "cand");
@@ -1242,9 +1169,9 @@ void sample_candidates_min_p(const Tensor& logits, const Tensor& temperature, co
   const int B = (int)logits.size(0), V = (int)logits.size(1);
   TORCH_CHECK(V <= 32768, "sampler supports V <= 32768 per rank");
   TORCH_CHECK(cand.dim() == 3 && cand.size(0) == B && cand.size(2) == 2, "cand must be [B, nchunks, 2]");
-  dsse::SampleParams p = sample_params(temperature, top_k, top_p, seeds, positions, active, B);
-  control_state(p, ctl_meta, c10::nullopt);
-  control_rows(p, row_slot, B);
+  dsse::SampleParams p = sample_params(temperature, top_k, top_p, seeds, positions, B);
+  if (ctl_meta != nullptr) control_state(p, *ctl_meta, c10::nullopt);
+  bind_rows(p, active, row_slot, B, ctl_meta != nullptr ? p.ctl_slots : B);
   p.logits = logits.data_ptr<float>();
   p.ld = V;
   p.V = V;
@@ -1252,6 +1179,21 @@ void sample_candidates_min_p(const Tensor& logits, const Tensor& temperature, co
   p.cand = reinterpret_cast<float2*>(cand.data_ptr<float>());
   p.nchunks = (int)cand.size(1);
   DSSE_CHECK_HIP(dsse_sample(B, &p, cur_stream()));
+}
+
+void sample_candidates(const Tensor& logits, const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
+                       const Tensor& seeds, const Tensor& positions, const c10::optional<Tensor>& active,
+                       Tensor& cand, int64_t vocab_offset) {
+  sample_candidates_impl(logits, temperature, top_k, top_p, seeds, positions, active, cand, nullptr, c10::nullopt,
+                         vocab_offset);
+}
+
+void sample_candidates_min_p(const Tensor& logits, const Tensor& temperature, const Tensor& top_k, const Tensor& top_p,
+                             const Tensor& seeds, const Tensor& positions, const c10::optional<Tensor>& active,
+                             Tensor& cand, const Tensor& ctl_meta, const c10::optional<Tensor>& row_slot,
+                             int64_t vocab_offset) {
+  sample_candidates_impl(logits, temperature, top_k, top_p, seeds, positions, active, cand, &ctl_meta, row_slot,
+                         vocab_offset);
 }
 
 // ---- guided decoding (sampler.hip guide_live / sample_guide_mask / sample_guide_advance; records: api.h) ---------
@@ -1292,24 +1234,6 @@ dsse::GuideParams guide_params(const Tensor& tok_bytes, const Tensor& tok_len, c
   return p;
 }
 
-void guide_rows(dsse::GuideParams& p, const c10::optional<Tensor>& active, const c10::optional<Tensor>& row_slot,
-                int B) {
-  if (active.has_value()) {
-    check_gpu(*active, "active");
-    check_dtype(*active, at::kInt, "active");
-    TORCH_CHECK(active->is_contiguous() && active->numel() >= B, "active too short");
-    p.active = active->data_ptr<int>();
-  }
-  if (row_slot.has_value()) {
-    check_gpu(*row_slot, "row_slot");
-    check_dtype(*row_slot, at::kInt, "row_slot");
-    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
-    p.row_slot = row_slot->data_ptr<int>();
-  } else {
-    TORCH_CHECK(B <= p.slots, "more rows than slots (no row_slot map)");
-  }
-}
-
 // Once per table upload, on the stream, before first use: the stuck bits of pool entry `entry`'s first n_states states.
 void guide_live(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& guide_tab, Tensor& guide_flags,
                 const Tensor& guide_meta, int64_t entry, int64_t n_states, int64_t eos) {
@@ -1325,19 +1249,10 @@ void sample_guide_mask(Tensor& logits, const c10::optional<Tensor>& active, cons
                        const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
                        const Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t vocab_offset,
                        int64_t eos) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");
-  check_dtype(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
-                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
-  const int B = (int)logits.size(0), V = (int)logits.size(1);
-  TORCH_CHECK(V >= 1 && V <= 32768, "sampler supports V <= 32768 per rank");
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
-  TORCH_CHECK(vocab_offset >= 0 && vocab_offset <= INT32_MAX - 32768, "bad vocab_offset");
-  guide_rows(p, active, row_slot, B);
-  p.logits = logits.data_ptr<float>();
-  p.ld = (int)logits.stride(0);
-  p.V = V;
-  p.vocab_offset = (int)vocab_offset;
+  p.logits = bind_logits(p, logits, vocab_offset);
+  const int B = (int)logits.size(0);
+  bind_rows(p, active, row_slot, B, p.slots);
   DSSE_CHECK_HIP(dsse_sample_guide_mask(B, &p, cur_stream()));
 }
 
@@ -1350,15 +1265,16 @@ void sample_guide_advance(const Tensor& ids, const c10::optional<Tensor>& active
   TORCH_CHECK(ids.is_contiguous() && ids.numel() <= INT32_MAX, "ids must be contiguous");
   const int B = (int)ids.numel();
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
-  guide_rows(p, active, row_slot, B);
+  bind_rows(p, active, row_slot, B, p.slots);
   p.ids = ids.data_ptr<int>();
   DSSE_CHECK_HIP(dsse_sample_guide_advance(B, &p, cur_stream()));
 }
 
-// sample_pick whose picked token also joins hist[b] where slot b has penalties on.
-void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
+// Merge pass over cand_all [world, B, nchunks, 2] and commit: next_ids, ring[head], positions += 1.  With the penalty
+// state (sample_pick_hist) the picked token also joins hist[b] where slot b has penalties on.
+void sample_pick_impl(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
                       const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
-                      const c10::optional<Tensor>& positions_inc, const Tensor& pen_meta, const Tensor& hist,
+                      const c10::optional<Tensor>& positions_inc, const Tensor* pen_meta, const Tensor* hist,
                       int64_t vocab) {
   check_gpu(cand_all, "cand_all");
   check_gpu(next_ids, "next_ids");
@@ -1366,9 +1282,9 @@ void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& activ
   TORCH_CHECK(cand_all.dim() == 4 && cand_all.size(3) == 2, "cand_all must be [world, B, nchunks, 2]");
   const int world = (int)cand_all.size(0), B = (int)cand_all.size(1);
   TORCH_CHECK(next_ids.numel() >= B, "next_ids too short");
-  dsse::SampleParams p{};
-  penalty_state(p, pen_meta, hist);
-  penalty_rows(p, active, c10::nullopt, B);
+  dsse::SampleParams p{};  // penalty state null without
+  if (hist != nullptr) penalty_state(p, *pen_meta, *hist);
+  bind_rows(p, active, c10::nullopt, B, hist != nullptr ? p.pen_slots : B);
   p.nchunks = (int)cand_all.size(2);
   p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
   p.next_ids = next_ids.data_ptr<int>();
@@ -1388,6 +1304,19 @@ void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& activ
   DSSE_CHECK_HIP(dsse_sample_pick(B, world, cand_all.data_ptr(), &p, cur_stream()));
 }
 
+void sample_pick(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
+                 const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
+                 const c10::optional<Tensor>& positions_inc, int64_t vocab) {
+  sample_pick_impl(cand_all, active, next_ids, ring, ring_counter, positions_inc, nullptr, nullptr, vocab);
+}
+
+void sample_pick_hist(const Tensor& cand_all, const c10::optional<Tensor>& active, Tensor& next_ids,
+                      const c10::optional<Tensor>& ring, const c10::optional<Tensor>& ring_counter,
+                      const c10::optional<Tensor>& positions_inc, const Tensor& pen_meta, const Tensor& hist,
+                      int64_t vocab) {
+  sample_pick_impl(cand_all, active, next_ids, ring, ring_counter, positions_inc, &pen_meta, &hist, vocab);
+}
+
 // new_ids[i] joins the history of slot row_slot[i] (else i): the eager first-token path.
 void sample_hist_append(const Tensor& new_ids, const c10::optional<Tensor>& row_slot,
                         const c10::optional<Tensor>& active, const Tensor& pen_meta, Tensor& hist) {
@@ -1397,7 +1326,7 @@ void sample_hist_append(const Tensor& new_ids, const c10::optional<Tensor>& row_
   const int n = (int)new_ids.numel();
   dsse::SampleParams p{};
   penalty_state(p, pen_meta, hist);
-  penalty_rows(p, active, row_slot, n);
+  bind_rows(p, active, row_slot, n, p.pen_slots);
   DSSE_CHECK_HIP(dsse_sample_hist_append(n, new_ids.data_ptr<int>(), &p, cur_stream()));
 }
 
@@ -1456,34 +1385,7 @@ void logprob_rows(dsse::LogprobParams& p, const c10::optional<Tensor>& active, c
   TORCH_CHECK(lp_meta.is_contiguous() && lp_meta.numel() >= 1, "lp_meta must be a contiguous [slots]");
   p.lp_meta = lp_meta.data_ptr<int>();
   p.slots = (int)lp_meta.numel();
-  if (active.has_value()) {
-    check_gpu(*active, "active");
-    check_dtype(*active, at::kInt, "active");
-    TORCH_CHECK(active->is_contiguous() && active->numel() >= B, "active too short");
-    p.active = active->data_ptr<int>();
-  }
-  if (row_slot.has_value()) {
-    check_gpu(*row_slot, "row_slot");
-    check_dtype(*row_slot, at::kInt, "row_slot");
-    TORCH_CHECK(row_slot->is_contiguous() && row_slot->numel() >= B, "row_slot too short");
-    p.row_slot = row_slot->data_ptr<int>();
-  } else {
-    TORCH_CHECK(B <= p.slots, "more rows than slots (no row_slot map)");
-  }
-}
-
-void logprob_logits(dsse::LogprobParams& p, const Tensor& logits, int64_t vocab_offset, int64_t vocab) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be a GPU tensor");  // (rows may be strided: a column slice of a shard)
-  check_dtype(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1) &&
-                  logits.stride(0) <= INT32_MAX, "logits must be [B, V] with unit column stride");
-  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= 32768, "sampler supports V <= 32768 per rank");
-  TORCH_CHECK(vocab_offset >= 0 && vocab_offset <= INT32_MAX - 32768, "vocab_offset out of range");
-  p.logits = logits.data_ptr<float>();
-  p.ld = (int)logits.stride(0);
-  p.V = (int)logits.size(1);
-  p.vocab_offset = (int)vocab_offset;
-  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
+  bind_rows(p, active, row_slot, B, p.slots);
 }
 
 // Per-rank pass over logits [B, V] BEFORE the penalty pass: rec [B, 42] = [max | sum exp(x - max) | 20 x (logit, id
@@ -1493,7 +1395,8 @@ void logprob_stats(const Tensor& logits, const c10::optional<Tensor>& active, co
                    const c10::optional<Tensor>& row_slot, Tensor& rec, const c10::optional<Tensor>& raw,
                    int64_t vocab_offset) {
   dsse::LogprobParams p{};
-  logprob_logits(p, logits, vocab_offset, INT32_MAX);
+  p.logits = bind_logits(p, logits, vocab_offset);
+  p.v_global = INT32_MAX;
   const int B = (int)logits.size(0);
   logprob_rows(p, active, lp_meta, row_slot, B);
   check_gpu(rec, "rec");
@@ -1516,7 +1419,8 @@ void logprob_chosen(const Tensor& logits, const Tensor& next_ids, const c10::opt
                     const Tensor& lp_meta, const c10::optional<Tensor>& row_slot, Tensor& chosen,
                     int64_t vocab_offset, int64_t vocab) {
   dsse::LogprobParams p{};
-  logprob_logits(p, logits, vocab_offset, vocab);
+  p.logits = bind_logits(p, logits, vocab_offset);
+  p.v_global = (int)std::min<int64_t>(vocab, INT32_MAX);
   const int B = (int)logits.size(0);
   logprob_rows(p, active, lp_meta, row_slot, B);
   check_gpu(next_ids, "next_ids");

@@ -30,6 +30,7 @@ import math
 import os
 import time
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -187,6 +188,24 @@ class PrefillSeq:
     last_chunk: bool        # sample a token after this chunk
 
 
+class SampleSite(NamedTuple):
+    """The operands in which the three sampling sites differ (ModelRunner._sample runs the passes over them)."""
+    logits: torch.Tensor        # fp32 [rows, local vocab]; the bias, penalty and guide passes rewrite it in place
+    active: object              # int32 [rows], or None: every row samples
+    row_slot: object            # int32 [rows]: row i samples for slot row_slot[i]; None: row i is slot i
+    temperature: torch.Tensor   # the rows' sampling parameters ...
+    top_k: torch.Tensor
+    top_p: torch.Tensor
+    seeds: torch.Tensor
+    positions: torch.Tensor     # ... and the position of each row's predecessor token
+    cand: torch.Tensor          # fp32 [rows, chunks, 2]: this rank's candidates
+    cand_all: object            # fp32 [TP, rows, chunks, 2]: their all-gathered form (read when TP > 1)
+    lp_bufs: object             # _lp_alloc's buffers for these rows (read once logprobs are in use)
+    ids: torch.Tensor           # int32 [rows]: where the commit writes the sampled tokens
+    ring: dict                  # logprob_finish's ring_* keyword: the ring row the tokens go to
+    commit: str                 # "decode" | "graph" | "eager": the commit ops of the site (_sample)
+
+
 class ModelRunner:
     def __init__(self, w: EngineWeights, num_blocks: int, max_batch: int = 64, max_model_len: int = 4096,
                  max_prefill_tokens: int = 8192, device="cuda", comm: TPComm | None = None, use_graphs=None,
@@ -312,12 +331,12 @@ class ModelRunner:
         self.pf_graphs = {}   # row bucket -> captured prefill graph
         self.pf = None        # static prefill buffers (allocated by capture)
         self.mx_graphs = {}   # decode bucket B -> [(chunk rows C, captured mixed prefill + decode graph)], C ascending
-        # their twins per (penalties used, logprobs used[, True: the bias and ban pass / min_p used]), each captured
-        # the first time that combination is needed (_capture_twins); pen_* = the (True, False) set: the penalty pass
-        # and nothing else new
+        # their twins per pass set (_twin_key: penalties, logprobs, the bias and ban pass / min_p, guides in use), each
+        # captured the first time that combination is needed (_capture_twins); pen_* = the (True, False, False, False)
+        # set: the penalty pass and nothing else new
         self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs = {}, {}, {}
-        self._twins = {(True, False): (self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs)}
-        self._captured_key = (False, False)  # the passes the graphs of capture() hold (set there)
+        self._twins = {(True, False, False, False): (self.pen_graphs, self.pen_pf_graphs, self.pen_mx_graphs)}
+        self._captured_key = (False, False, False, False)  # the passes the graphs of capture() hold (set there)
         self.host_trace = None  # a list: host seconds of each graph-replayed mixed step (upload, replay, sampling)
 
     # ------------------------------------------------------------------ decode
@@ -418,45 +437,61 @@ class ModelRunner:
             self.comm.all_reduce_rmsnorm(tmp, resid, norm_w, x, eps)
 
     def _sample_commit(self, B: int) -> None:
-        """Candidates per (row, vocab chunk) on each rank -> (TP: all-gather, 8 B per candidate) -> pick."""
+        """The decode step's sampling (decode and mixed graphs): row b is slot b, the pick commits ids / ring row /
+        positions itself."""
         r = slice(0, B)
-        cand = self._cand[B]
-        # penalties first (rows with neutral parameters return at once); the pick appends to the penalised histories.
-        # The pass is launched (and captured: _capture_penalty_graphs) only once a request has asked for penalties
-        # logprob statistics before them: the penalty pass rewrites logits in place (same lazy launch / capture)
-        if self.lp_used:
-            raw = self._logprob_stats(self.logits[r], self.active[r], None, self._lp_bufs[B])
-        if self.ctl_used:  # (same lazy launch / capture) logit_bias and the min_tokens ban: after the raw statistics
-            ops.sample_bias_ban(self.logits[r], self.active[r], self.ctl_meta, self.ctl_body, self.positions[r], None,
-                                self.w.vocab_offset, self.cfg.vocab_size)
-        if self.hist_used:
-            ops.sample_penalties(self.logits[r], self.active[r], self.pen_meta, self.hist_state, None,
-                                 self.w.vocab_offset, self.cfg.vocab_size)
-        if self.guide_used:  # (same lazy launch / capture) the guide's token mask: last before the candidates
-            self._guide_mask(self.logits[r], self.active[r], None)
-        self._candidates(self.logits[r], self.temperature[r], self.top_k[r], self.top_p[r], self.seeds[r],
-                         self.positions[r], self.active[r], cand, None)
-        if self.comm.size == 1:
-            cand_all = cand.unsqueeze(0)
-        else:
-            cand_all = self._cand_all[B]
-            self.comm.all_gather_into(cand_all, cand)
-        ops.sample_pick_hist(cand_all, self.active[r], self.ids[r], self.ring, self.ring_counter, self.positions[r],
-                             self.pen_meta, self.hist_state, vocab=self.cfg.vocab_size)
-        if self.guide_used:  # the committed token advances its slot's DFA state
-            self._guide_advance(self.ids[r], self.active[r], None)
-        if self.lp_used:  # (before ring_advance: the same ring row the pick wrote)
-            self._logprob_finish(self.logits[r], raw, self.ids[r], self.active[r], None, self._lp_bufs[B],
-                                 ring_counter=self.ring_counter)
+        self._sample(SampleSite(self.logits[r], self.active[r], None, self.temperature[r], self.top_k[r],
+                                self.top_p[r], self.seeds[r], self.positions[r], self._cand[B], self._cand_all[B],
+                                self._lp_bufs[B], self.ids[r], dict(ring_counter=self.ring_counter), "decode"))
 
-    def _candidates(self, logits, temperature, top_k, top_p, seeds, positions, active, cand, row_slot) -> None:
-        """The candidate pass; with min_p (ctl_meta's fourth column, slot-indexed) once a request has used it."""
-        if self.ctl_used:
-            ops.sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions, active, cand,
-                                        self.ctl_meta, row_slot, self.w.vocab_offset)
+    def _sample(self, s: SampleSite) -> None:
+        """Every sampling site's passes, in the one order they have (docs/kernels.md, "Sampler"):
+
+            logprob stats -> bias / ban -> penalties -> guide mask -> candidates (with min_p once the bias and ban
+            pass is in use) -> (TP: all-gather, 8 B per candidate) -> the site's commit -> guide advance -> logprob
+            chosen / finish
+
+        The statistics come first because the next three passes rewrite the logits in place; the guide mask is last
+        before the candidates so that nothing un-masks a token; the two passes after the commit read the committed
+        ids only.  Each optional pass is launched (and captured: _capture_twins) only once a request has asked for
+        its feature; rows with neutral parameters return at once."""
+        w, cfg, comm = self.w, self.cfg, self.comm
+        if self.lp_used:
+            raw = self._logprob_stats(s.logits, s.active, s.row_slot, s.lp_bufs)
+        if self.ctl_used:  # logit_bias and the min_tokens ban
+            ops.sample_bias_ban(s.logits, s.active, self.ctl_meta, self.ctl_body, s.positions, s.row_slot,
+                                w.vocab_offset, cfg.vocab_size)
+        if self.hist_used:
+            # (first-token sites after a re-prefill: the tokens already published count, the engine uploaded them
+            # with the history)
+            ops.sample_penalties(s.logits, s.active, self.pen_meta, self.hist_state, s.row_slot, w.vocab_offset,
+                                 cfg.vocab_size)
+        if self.guide_used:
+            self._guide_mask(s.logits, s.active, s.row_slot)
+        rows = (s.logits, s.temperature, s.top_k, s.top_p, s.seeds, s.positions, s.active, s.cand)
+        if self.ctl_used:  # min_p: ctl_meta's fourth column, slot-indexed
+            ops.sample_candidates_min_p(*rows, self.ctl_meta, s.row_slot, w.vocab_offset)
         else:
-            ops.sample_candidates(logits, temperature, top_k, top_p, seeds, positions, active, cand,
-                                  self.w.vocab_offset)
+            ops.sample_candidates(*rows, w.vocab_offset)
+        if comm.size == 1:
+            cand_all = s.cand.unsqueeze(0)
+        else:
+            cand_all = s.cand_all
+            comm.all_gather_into(cand_all, s.cand)
+        if s.commit == "decode":  # the pick also writes the ring row, positions += 1 and the penalised histories
+            ops.sample_pick_hist(cand_all, s.active, s.ids, self.ring, self.ring_counter, s.positions, self.pen_meta,
+                                 self.hist_state, vocab=cfg.vocab_size)
+        else:
+            ops.sample_pick(cand_all, s.active, s.ids, vocab=cfg.vocab_size)
+            if s.commit == "graph":
+                ops.prefill_sample_commit_hist(self.pf.samp_meta(), s.ids, self.ids, self.ring, self.positions,
+                                               self.pen_meta, self.hist_state)
+            elif self.hist_used:  # "eager": the site copies ids / ring row / positions itself
+                ops.sample_hist_append(s.ids, s.row_slot, None, self.pen_meta, self.hist_state)
+        if self.guide_used:  # the committed token advances its slot's DFA state
+            self._guide_advance(s.ids, s.active, s.row_slot)
+        if self.lp_used:  # (decode: before ring_advance, the same ring row the pick wrote)
+            self._logprob_finish(s.logits, raw, s.ids, s.active, s.row_slot, s.lp_bufs, **s.ring)
 
     # ------------------------------------------------------------------ logprobs
     def _lp_alloc(self, n: int) -> dict:
@@ -609,18 +644,43 @@ class ModelRunner:
                           row_slot, self.guide_eos)
 
     def _twin_key(self) -> tuple:
-        if self.guide_used:  # the fourth flag: the guide's mask and advance passes
-            return (self.hist_used, self.lp_used, self.ctl_used, True)
-        return (self.hist_used, self.lp_used) + ((True,) if self.ctl_used else ())
+        """The pass set in use: (penalties, logprobs, the bias and ban pass / min_p, the guide passes)."""
+        return (self.hist_used, self.lp_used, self.ctl_used, self.guide_used)
+
+    def _capture_graphs(self, shapes, body) -> list:
+        """Capture body(shape) into a new graph in the shared pool, largest shape first (the first graph ever
+        captured hands its pool to the rest).  Returns [(shape, graph)] in capture order."""
+        out = []
+        for shape in sorted(shapes, reverse=True):
+            g = torch.cuda.CUDAGraph()
+            with _capture(g, pool=self.graph_pool):
+                body(shape)
+            if self.graph_pool is None:
+                self.graph_pool = g.pool()
+            out.append((shape, g))
+        return out
+
+    def _prefill_graph_body(self, tb: int) -> None:
+        self._prefill_layers(tb, self.pf.views(tb))
+        self._graph_sample()
+
+    def _mixed_graph_body(self, shape: tuple) -> None:
+        self._mixed_layers(*shape)
+        self._graph_sample()
+
+    def _capture_mixed_graphs(self, pairs, out: dict) -> None:
+        """out[B] = [(C, graph), ...] by ascending C for the (B, C) in `pairs`."""
+        for (B, C), g in self._capture_graphs(pairs, self._mixed_graph_body):
+            out.setdefault(B, []).insert(0, (C, g))
 
     def _capture_twins(self) -> None:
-        """The first request that needs a new combination of (penalties, logprobs): every captured graph gets a twin
-        with the penalty pass in front of the candidates and / or the logprob passes around them, replayed from now
-        on; until then the graphs captured at startup run, which hold no such launch and no extra collective (an
-        early-exit launch per step measured +8 us on the 4.23 ms 64-stream step: profiles/r7/penalties.md).  At most
-        three such captures in a process's life (seven with the bias and ban pass / min_p, the key's third flag).  Stream capture executes nothing, so no decode state changes; the
-        shapes and buffers are the ones the startup capture warmed, and the logprob all-gathers run once eagerly
-        first.  Deterministic across a TP group: every rank admits the same request in the same step."""
+        """The first request that needs a new pass set (_twin_key): every captured graph gets a twin with the passes
+        in use (_sample), replayed from now on; until then the graphs captured at startup run, which hold no such
+        launch and no extra collective (an early-exit launch per step measured +8 us on the 4.23 ms 64-stream step:
+        profiles/r7/penalties.md).  The key names 15 pass sets besides the empty one, each captured at most once
+        between two capture() calls.  Stream capture executes nothing, so no decode state changes; the shapes and
+        buffers are the ones the startup capture warmed, and the logprob all-gathers run once eagerly first.
+        Deterministic across a TP group: every rank admits the same request in the same step."""
         key = self._twin_key()
         if key[:2] == (True, True) and self._lp_raw is None:
             self._lp_raw = torch.zeros(max(self.max_batch, PREFILL_GRAPH_SEQS), self.w.vocab_local,
@@ -634,23 +694,9 @@ class ModelRunner:
                 self.comm.all_gather_into(bufs["rec_all"], bufs["rec"])
                 self.comm.all_gather_into(bufs["chosen_all"], bufs["chosen"])
         t0 = time.perf_counter()
-        for B in sorted(self.graphs, reverse=True):
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, pool=self.graph_pool):
-                self.decode_forward(B)
-            dec[B] = g
-        for tb in sorted(self.pf_graphs, reverse=True):
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, pool=self.graph_pool):
-                self._prefill_layers(tb, self.pf.views(tb))
-                self._graph_sample()
-            pfg[tb] = g
-        for B, C in sorted(((B, C) for B, lst in self.mx_graphs.items() for C, _ in lst), reverse=True):
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, pool=self.graph_pool):
-                self._mixed_layers(B, C)
-                self._graph_sample()
-            mxg.setdefault(B, []).insert(0, (C, g))
+        dec.update(self._capture_graphs(self.graphs, self.decode_forward))
+        pfg.update(self._capture_graphs(self.pf_graphs, self._prefill_graph_body))
+        self._capture_mixed_graphs([(B, C) for B, lst in self.mx_graphs.items() for C, _ in lst], mxg)
         torch.cuda.synchronize(self.device)
         self.twin_capture_s = time.perf_counter() - t0
         if self.comm.rank == 0:
@@ -771,13 +817,7 @@ class ModelRunner:
                 self.decode_forward(B)
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
-        for B in sorted(buckets, reverse=True):
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, pool=self.graph_pool):
-                self.decode_forward(B)
-            if self.graph_pool is None:
-                self.graph_pool = g.pool()
-            self.graphs[B] = g
+        self.graphs.update(self._capture_graphs(buckets, self.decode_forward))
         torch.cuda.synchronize(self.device)
         self._restore_state(saved)
         if prefill_graphs:
@@ -798,18 +838,10 @@ class ModelRunner:
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for tb in buckets:
-                self._prefill_layers(tb, self.pf.views(tb))
-                self._graph_sample()  # padding metadata: no prompt finishes, nothing is committed
+                self._prefill_graph_body(tb)  # padding metadata: no prompt finishes, nothing is committed
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
-        for tb in sorted(buckets, reverse=True):
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, pool=self.graph_pool):
-                self._prefill_layers(tb, self.pf.views(tb))
-                self._graph_sample()
-            if self.graph_pool is None:
-                self.graph_pool = g.pool()
-            self.pf_graphs[tb] = g
+        self.pf_graphs.update(self._capture_graphs(buckets, self._prefill_graph_body))
         torch.cuda.synchronize(self.device)
         if mixed_mode() != "0" and os.environ.get("DSSE_MIXED_GRAPHS", "1") != "0":
             self._capture_mixed(list(decode_buckets))
@@ -842,17 +874,11 @@ class ModelRunner:
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            for B, C in pairs:  # eager warm-up of every shape (kernel attributes, library state)
-                self._mixed_layers(B, C)
-                self._graph_sample()
+            for pair in pairs:  # eager warm-up of every shape (kernel attributes, library state)
+                self._mixed_graph_body(pair)
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
-        for B, C in sorted(pairs, reverse=True):
-            g = torch.cuda.CUDAGraph()
-            with _capture(g, pool=self.graph_pool):
-                self._mixed_layers(B, C)
-                self._graph_sample()
-            self.mx_graphs.setdefault(B, []).insert(0, (C, g))
+        self._capture_mixed_graphs(pairs, self.mx_graphs)
         torch.cuda.synchronize(self.device)
         self._restore_state(saved)
 
@@ -877,17 +903,20 @@ class ModelRunner:
         if self.device.type == "cuda":  # pinned + non_blocking: no host wait for the decode steps already queued
             idx = idx.pin_memory().to(self.device, non_blocking=True)
         si, di = idx[0], idx[1]
-        # the token histories (length word + tokens) travel with their slots once any sequence has used penalties
-        for t in (self.ids, self.positions) + ((self.hist_state,) if self.hist_used else ()) + \
-                ((self.lp_meta,) if self.lp_used else ()):
-            t.index_copy_(0, di, t.index_select(0, si))
-        if self.ctl_used:  # the bias / ban records and their ctl_meta columns travel too
-            self.ctl_body.index_copy_(0, di, self.ctl_body.index_select(0, si))
-            m = self.ctl_meta.view(4, -1)
-            m.index_copy_(1, di, m.index_select(1, si))
-        if self.guide_used:  # the pool index and the device-owned DFA state
-            m = self.guide_meta.view(2, -1)
-            m.index_copy_(1, di, m.index_select(1, si))
+        for t, dim in self._slot_arrays():
+            t.index_copy_(dim, di, t.index_select(dim, si))
+
+    def _slot_arrays(self) -> list:
+        """[(tensor, the dimension that indexes slots)]: the device state that travels with a sequence when its slot
+        moves (the host-owned slot_meta / pen_meta are re-uploaded by the engine).  A feature's arrays travel once a
+        request has used it; a new per-slot array needs one line here."""
+        hist, lp, ctl, guide = self._twin_key()
+        arrays = [(self.ids, 0), (self.positions, 0)]
+        arrays += [(self.hist_state, 0)] if hist else []  # the token histories: length word + tokens
+        arrays += [(self.lp_meta, 0)] if lp else []
+        arrays += [(self.ctl_body, 0), (self.ctl_meta.view(4, -1), 1)] if ctl else []  # bias / ban records + columns
+        arrays += [(self.guide_meta.view(2, -1), 1)] if guide else []  # the pool index and the device-owned DFA state
+        return arrays
 
     def decode(self, B: int) -> None:
         g = self._graph_set()[0].get(B)
@@ -1066,7 +1095,7 @@ class ModelRunner:
     def _prefill_sample(self, seqs: list, x, q_start: list, q_len: list, ring_row: int) -> None:
         """Sequences whose last chunk this is sample their first token (rows q_start + q_len - 1 of `x`) into
         ids[slot] and ring[ring_row, slot]; positions[slot] is set on the device."""
-        w, cfg, comm, dev = self.w, self.cfg, self.comm, self.device
+        w, comm, dev = self.w, self.comm, self.device
         last = [i for i, s in enumerate(seqs) if s.last_chunk]
         if not last:
             return
@@ -1084,39 +1113,16 @@ class ModelRunner:
         logits = torch.empty(nL, w.vocab_local, **f32)
         ops.gemm_out(xl, w.lm_head_t, logits)
         new_ids = torch.zeros(nL, dtype=torch.int32, device=dev)
-        temp = self.temperature.index_select(0, slot_idx)
-        tk = self.top_k.index_select(0, slot_idx)
-        tp = self.top_p.index_select(0, slot_idx)
-        sd = self.seeds.index_select(0, slot_idx).contiguous()
         nch = SAMPLE_CHUNKS if dev.type == "cuda" else 1
-        cand = torch.zeros(nL, nch, 2, **f32)
-        slot_i32 = slot_idx.to(torch.int32) if self.hist_used or self.lp_used or self.ctl_used or self.guide_used \
-            else None
-        if self.lp_used:  # (eager passes: nothing is launched until a request has asked for logprobs / penalties)
-            lp_bufs = self._lp_eager_bufs(nL)
-            raw = self._logprob_stats(logits, None, slot_i32, lp_bufs)
-        if self.ctl_used:
-            ops.sample_bias_ban(logits, None, self.ctl_meta, self.ctl_body, last_pos, slot_i32, w.vocab_offset,
-                                cfg.vocab_size)
-        if self.hist_used:
-            # after a re-prefill the tokens already published count: the engine uploaded them with the history
-            ops.sample_penalties(logits, None, self.pen_meta, self.hist_state, slot_i32, w.vocab_offset,
-                                 cfg.vocab_size)
-        if self.guide_used:
-            self._guide_mask(logits, None, slot_i32)
-        self._candidates(logits, temp, tk, tp, sd, last_pos, None, cand, slot_i32)
-        if comm.size == 1:
-            cand_all = cand.unsqueeze(0)
-        else:
-            cand_all = torch.zeros(comm.size, nL, nch, 2, **f32)
-            comm.all_gather_into(cand_all, cand)
-        ops.sample_pick(cand_all, None, new_ids, vocab=cfg.vocab_size)
-        if self.hist_used:
-            ops.sample_hist_append(new_ids, slot_i32, None, self.pen_meta, self.hist_state)
-        if self.lp_used:
-            self._logprob_finish(logits, raw, new_ids, None, slot_i32, lp_bufs, ring_row=ring_row)
-        if self.guide_used:
-            self._guide_advance(new_ids, None, slot_i32)
+        slot_i32 = slot_idx.to(torch.int32) if any(self._twin_key()) else None
+        # (eager passes: nothing is launched or allocated until a request has asked for its feature)
+        self._sample(SampleSite(logits, None, slot_i32, self.temperature.index_select(0, slot_idx),
+                                self.top_k.index_select(0, slot_idx), self.top_p.index_select(0, slot_idx),
+                                self.seeds.index_select(0, slot_idx).contiguous(), last_pos,
+                                torch.zeros(nL, nch, 2, **f32),
+                                torch.zeros(comm.size, nL, nch, 2, **f32) if comm.size > 1 else None,
+                                self._lp_eager_bufs(nL) if self.lp_used else None, new_ids,
+                                dict(ring_row=ring_row), "eager"))
         self.ids.index_copy_(0, slot_idx, new_ids)
         self.ring[ring_row].index_copy_(0, slot_idx, new_ids)
         self.positions.index_copy_(0, slot_idx, last_pos + 1)
@@ -1175,38 +1181,15 @@ class ModelRunner:
         (prefill_sample_gather), LM head, candidates (TP: all-gathered), pick, commit ids / ring row / positions
         (prefill_sample_commit) -- static shapes of PREFILL_GRAPH_SEQS rows, rows past the batch's count inactive.
         Replaces _prefill_sample's torch index kernels and per-call index upload on the graph paths."""
-        pf, w, cfg, comm = self.pf, self.w, self.cfg, self.comm
-        ns = pf.ns
+        pf, ns = self.pf, self.pf.ns
         meta, sm = pf.samp_meta(), pf.s_meta
         ops.prefill_sample_gather(pf.x, meta, self.slot_meta, pf.s_xl, sm)
-        ops.gemm_out(pf.s_xl, w.lm_head_t, pf.s_logits)
-        active = sm[:ns]
-        if self.lp_used:
-            raw = self._logprob_stats(pf.s_logits, active, meta[ns:2 * ns], self._lp_pf)
-        if self.ctl_used:  # gathered row i samples for slot meta[ns + i]: its bias / ban record, penalties, history
-            ops.sample_bias_ban(pf.s_logits, active, self.ctl_meta, self.ctl_body, sm[6 * ns:7 * ns], meta[ns:2 * ns],
-                                w.vocab_offset, cfg.vocab_size)
-        if self.hist_used:
-            ops.sample_penalties(pf.s_logits, active, self.pen_meta, self.hist_state, meta[ns:2 * ns],
-                                 w.vocab_offset, cfg.vocab_size)
-        if self.guide_used:
-            self._guide_mask(pf.s_logits, active, meta[ns:2 * ns])
-        self._candidates(pf.s_logits, sm[ns:2 * ns].view(torch.float32), sm[2 * ns:3 * ns],
-                         sm[3 * ns:4 * ns].view(torch.float32), sm[4 * ns:6 * ns].view(ns, 2), sm[6 * ns:7 * ns],
-                         active, pf.s_cand, meta[ns:2 * ns])
-        if comm.size == 1:
-            cand_all = pf.s_cand.unsqueeze(0)
-        else:
-            cand_all = pf.s_cand_all
-            comm.all_gather_into(cand_all, pf.s_cand)
-        ops.sample_pick(cand_all, active, pf.s_new, vocab=cfg.vocab_size)
-        ops.prefill_sample_commit_hist(meta, pf.s_new, self.ids, self.ring, self.positions, self.pen_meta,
-                                       self.hist_state)
-        if self.guide_used:
-            self._guide_advance(pf.s_new, active, meta[ns:2 * ns])
-        if self.lp_used:
-            self._logprob_finish(pf.s_logits, raw, pf.s_new, active, meta[ns:2 * ns], self._lp_pf,
-                                 ring_row_dev=meta[3 * ns + 1:3 * ns + 2])
+        ops.gemm_out(pf.s_xl, self.w.lm_head_t, pf.s_logits)
+        # gathered row i samples for slot meta[ns + i]: its bias / ban record, penalties, history, guide, logprobs
+        self._sample(SampleSite(pf.s_logits, sm[:ns], meta[ns:2 * ns], sm[ns:2 * ns].view(torch.float32),
+                                sm[2 * ns:3 * ns], sm[3 * ns:4 * ns].view(torch.float32),
+                                sm[4 * ns:6 * ns].view(ns, 2), sm[6 * ns:7 * ns], pf.s_cand, pf.s_cand_all,
+                                self._lp_pf, pf.s_new, dict(ring_row_dev=meta[3 * ns + 1:3 * ns + 2]), "graph"))
 
     def mixed(self, B: int, seqs: list, ring_row: int) -> None:
         """ONE forward over the decode slots [0, B) and the prefill chunks `seqs` (rows B .. B+T-1): every weight

@@ -322,8 +322,8 @@ def test_engine_first_logprobs_request_arrives_mid_stream(weights, gpu):
 
     plain, r0, _ = run(-1)
     got, r1, e1 = run(4)
-    assert not r0._twins.get((False, True)) and not r0.lp_used
-    assert set(r1._twins[(False, True)][0]) == set(r1.graphs) and not r1.pen_graphs
+    assert not r0._twins.get((False, True, False, False)) and not r0.lp_used
+    assert set(r1._twins[(False, True, False, False)][0]) == set(r1.graphs) and not r1.pen_graphs
     assert e1.stats["mixed_steps"] > 0
     for c in "ab":
         assert [ev.token_id for ev in got[c]] == [ev.token_id for ev in plain[c]]

@@ -225,7 +225,7 @@ def test_runner_obeys_bias_and_ban(eager_run):
 
 def test_runner_graph_replay_equals_eager(weights, gpu, eager_run):
     toks, r = _run(weights, gpu, True)
-    key = (False, False, True)
+    key = (False, False, True, False)
     assert r.graphs and r.pf_graphs and set(r._twins[key][0]) == set(r.graphs)
     assert set(r._twins[key][1]) == set(r.pf_graphs) and not r.pen_graphs
     assert r._graph_set()[0] is r._twins[key][0] and r._graph_set()[0] is not r.graphs
@@ -278,7 +278,7 @@ def test_engine_first_biased_request_arrives_mid_stream(weights, gpu):
 
     plain, r0 = run(False)
     got, r1 = run(True)
-    key = (False, False, True)
+    key = (False, False, True, False)
     assert not r0.ctl_used and key not in r0._twins and r0._graph_set()[0] is r0.graphs
     assert set(r1._twins[key][0]) == set(r1.graphs) and not r1.pen_graphs
     assert len(plain["a"]) == 30 and got["a"] == plain["a"]
