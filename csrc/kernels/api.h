@@ -171,10 +171,23 @@ struct LogprobParams {
 //     word [slots + slot] = the current DFA state, kGuideDead = dead.  The host writes both words when a sequence takes
 //     the slot (state = the walk over the tokens already published), stream-ordered; from then on only the advance
 //     kernel writes the state.  Pool entries are host-owned and reference-counted by live sequences.
+//
+// JSON mode (response_format json_object; the language J: docs/kernels.md, "Sampler") is a pushdown walk inside the
+// same two launches.  A slot whose guide_meta entry word is kGuideJson uses no pool entry; its state lives in
+//   json_state [4, slots] (int32): [lexical state q | depth 0..kJsonDepth | stack bits 0..31 | stack bits 32..63],
+//     q = kGuideDead = dead.  The stack holds one bit per open container (0 = object, 1 = array), innermost at bit 0.
+//   json_tab [n <= kJsonStates, 256] (uint16): entry = next state | action << 14, kGuideDead = no transition.  Action
+//     1 / 2 pushes an object / array bit (dead at depth kJsonDepth); action 3 pops, and the next state then comes from
+//     what the pop uncovers: kJsonDone at depth 0, else kJsonAfterObj / kJsonAfterArr by the new innermost bit.  The
+//     lexical states are split by context (in an object / in an array), so a closing byte always matches the top bit.
 constexpr int kGuideStates = 512;
 constexpr int kGuidePool = 32;     // resident patterns (32 x 512 x 256 x 2 B = 8 MiB)
 constexpr int kGuideTokBytes = 32;
 constexpr int kGuideDead = 0xFFFF;
+constexpr int kGuideJson = -2;     // guide_meta entry word of a JSON-mode slot
+constexpr int kJsonDepth = 64;
+constexpr int kJsonStates = 128;   // (the table built by ops/reference.py json_table has 85)
+constexpr int kJsonStart = 0, kJsonDone = 1, kJsonAfterObj = 2, kJsonAfterArr = 3;
 struct GuideParams {
   const unsigned char* tok_bytes;
   const unsigned char* tok_len;
@@ -192,6 +205,10 @@ struct GuideParams {
   const int* ids;          // [B] committed (global) ids
   // live pass
   int entry, n_states;     // the pool entry just uploaded and its used states
+  // JSON mode (both null: a kGuideJson slot is treated as guide off)
+  const unsigned short* json_tab;  // [json_states, 256]
+  int* json_state;                 // [4, slots]
+  int json_states;
 };
 
 }  // namespace dsse

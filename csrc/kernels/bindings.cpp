@@ -1234,6 +1234,25 @@ dsse::GuideParams guide_params(const Tensor& tok_bytes, const Tensor& tok_len, c
   return p;
 }
 
+// JSON mode: json_tab int16 (uint16 bits) [n <= 128, 256] and json_state int32 [4 x slots], given together or not at
+// all (without them a slot marked kGuideJson is treated as guide off).
+void guide_json(dsse::GuideParams& p, const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state) {
+  TORCH_CHECK(json_tab.has_value() == json_state.has_value(), "json_tab and json_state go together");
+  if (!json_tab.has_value()) return;
+  check_gpu(*json_tab, "json_tab");
+  check_dtype(*json_tab, at::kShort, "json_tab");
+  check_gpu(*json_state, "json_state");
+  check_dtype(*json_state, at::kInt, "json_state");
+  TORCH_CHECK(json_tab->dim() == 2 && json_tab->is_contiguous() && json_tab->size(1) == 256 &&
+                  json_tab->size(0) > dsse::kJsonAfterArr && json_tab->size(0) <= dsse::kJsonStates,
+              "json_tab must be a contiguous [4..128, 256]");
+  TORCH_CHECK(json_state->is_contiguous() && json_state->numel() == 4 * (int64_t)p.slots,
+              "json_state must be [4 x slots] for guide_meta's slots");
+  p.json_tab = reinterpret_cast<const unsigned short*>(json_tab->data_ptr<int16_t>());
+  p.json_state = json_state->data_ptr<int>();
+  p.json_states = (int)json_tab->size(0);
+}
+
 // Once per table upload, on the stream, before first use: the stuck bits of pool entry `entry`'s first n_states states.
 void guide_live(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& guide_tab, Tensor& guide_flags,
                 const Tensor& guide_meta, int64_t entry, int64_t n_states, int64_t eos) {
@@ -1248,8 +1267,9 @@ void guide_live(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& gu
 void sample_guide_mask(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& tok_bytes,
                        const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
                        const Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t vocab_offset,
-                       int64_t eos) {
+                       int64_t eos, const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state) {
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
+  guide_json(p, json_tab, json_state);
   p.logits = bind_logits(p, logits, vocab_offset);
   const int B = (int)logits.size(0);
   bind_rows(p, active, row_slot, B, p.slots);
@@ -1259,12 +1279,14 @@ void sample_guide_mask(Tensor& logits, const c10::optional<Tensor>& active, cons
 // After a commit: the guide state of row b's slot advances by ids[b] (global ids).
 void sample_guide_advance(const Tensor& ids, const c10::optional<Tensor>& active, const Tensor& tok_bytes,
                           const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
-                          Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t eos) {
+                          Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t eos,
+                          const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state) {
   check_gpu(ids, "ids");
   check_dtype(ids, at::kInt, "ids");
   TORCH_CHECK(ids.is_contiguous() && ids.numel() <= INT32_MAX, "ids must be contiguous");
   const int B = (int)ids.numel();
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
+  guide_json(p, json_tab, json_state);
   bind_rows(p, active, row_slot, B, p.slots);
   p.ids = ids.data_ptr<int>();
   DSSE_CHECK_HIP(dsse_sample_guide_advance(B, &p, cur_stream()));
@@ -1698,9 +1720,11 @@ TORCH_LIBRARY(dsse, m) {
   m.def("guide_live(Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, Tensor(a!) guide_flags, Tensor guide_meta, "
         "int entry, int n_states, int eos) -> ()");
   m.def("sample_guide_mask(Tensor(a!) logits, Tensor? active, Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, "
-        "Tensor guide_flags, Tensor guide_meta, Tensor? row_slot=None, int vocab_offset=0, int eos=-1) -> ()");
+        "Tensor guide_flags, Tensor guide_meta, Tensor? row_slot=None, int vocab_offset=0, int eos=-1, "
+        "Tensor? json_tab=None, Tensor? json_state=None) -> ()");
   m.def("sample_guide_advance(Tensor ids, Tensor? active, Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, "
-        "Tensor guide_flags, Tensor(a!) guide_meta, Tensor? row_slot=None, int eos=-1) -> ()");
+        "Tensor guide_flags, Tensor(a!) guide_meta, Tensor? row_slot=None, int eos=-1, Tensor? json_tab=None, "
+        "Tensor(b!)? json_state=None) -> ()");
   m.def("sample_pick_hist(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring, "
         "Tensor? ring_counter, Tensor(c!)? positions_inc, Tensor pen_meta, Tensor(d!) hist, "
         "int vocab=2147483647) -> ()");

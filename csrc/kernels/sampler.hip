@@ -290,16 +290,77 @@ DEV int guide_walk(const GuideParams& p, const unsigned short* __restrict__ tab,
   return state;
 }
 
-// The guide of row b: false = nothing to do (inactive row, guide off, dead state).
+// The guide of row b: false = nothing to do (inactive row, guide off, dead state).  A JSON-mode slot comes back with
+// entry = kGuideJson and its lexical state (json_load reads the rest).
 DEV bool guide_row(const GuideParams& p, int b, int* slot_out, int* entry_out, int* state_out) {
   if (p.active && !p.active[b]) return false;
   const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, p.slots, -1);
   if ((unsigned)slot >= (unsigned)p.slots) return false;
-  const int entry = DSSE_IDX(p.meta[slot], p.pool, -1);
+  const int raw = p.meta[slot];
+  if (raw == kGuideJson) {
+    if (!p.json_state || !p.json_tab) return false;
+    *slot_out = slot;
+    *entry_out = kGuideJson;
+    *state_out = p.json_state[slot];
+    return true;
+  }
+  const int entry = DSSE_IDX(raw, p.pool, -1);
   if ((unsigned)entry >= (unsigned)p.pool) return false;
   *slot_out = slot;
   *entry_out = entry;
   *state_out = p.meta[p.slots + slot];
+  return true;
+}
+
+// ---- JSON mode: the pushdown walk (api.h: json_tab / json_state) ---------------------------------------------------
+struct JsonState {
+  int q, depth;
+  unsigned long long stack;  // one bit per open container, innermost at bit 0: 0 = object, 1 = array
+};
+
+// The slot's state; false = dead or out of range (a state no host write or advance produces).
+DEV bool json_load(const GuideParams& p, int slot, JsonState* s) {
+  const int* w = p.json_state + slot;
+  s->q = w[0];
+  s->depth = w[p.slots];
+  s->stack = (unsigned long long)(unsigned)w[2 * (size_t)p.slots] |
+             ((unsigned long long)(unsigned)w[3 * (size_t)p.slots] << 32);
+  return (unsigned)s->q < (unsigned)p.json_states && (unsigned)s->depth <= (unsigned)kJsonDepth;
+}
+
+// One byte per step, as guide_walk: a dependent chain of 2-byte table reads (85 x 512 B, resident in the vector L1 /
+// L2).  False = the walk died: no transition, a push at depth kJsonDepth, a token of length 0 or above kGuideTokBytes.
+DEV bool json_walk(const GuideParams& p, JsonState& s, int g) {
+  const int len = p.tok_len[g];
+  if (len < 1 || len > kGuideTokBytes) return false;
+  const uint4* src = reinterpret_cast<const uint4*>(p.tok_bytes + (size_t)g * kGuideTokBytes);
+  const uint4 lo = src[0], hi = src[1];
+  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  int q = s.q, depth = s.depth;
+  unsigned long long stack = s.stack;
+#pragma unroll
+  for (int j = 0; j < kGuideTokBytes; ++j) {
+    if (j >= len) break;
+    const int byte = (w[j >> 2] >> (8 * (j & 3))) & 0xff;
+    const int e = p.json_tab[(size_t)q * 256 + byte];
+    if (e == kGuideDead) return false;
+    const int act = e >> 14;
+    q = e & 0x3fff;
+    if (act == 3) {  // pop: the next state is what the pop uncovers
+      if (depth < 1) return false;
+      --depth;
+      stack >>= 1;
+      q = depth == 0 ? kJsonDone : (stack & 1) ? kJsonAfterArr : kJsonAfterObj;
+    } else if (act) {  // push: 1 = object, 2 = array
+      if (depth >= kJsonDepth) return false;
+      ++depth;
+      stack = (stack << 1) | (unsigned long long)(act == 2);
+    }
+    if (q >= p.json_states) return false;  // (never written by the host: an entry out of range)
+  }
+  s.q = q;
+  s.depth = depth;
+  s.stack = stack;
   return true;
 }
 
@@ -325,10 +386,47 @@ __global__ void __launch_bounds__(kGuideThreads) guide_live_kernel(GuideParams p
 // row bit-identical.  Otherwise column v (global id g = v + vocab_offset) keeps its bits iff g is allowed: EOS iff the
 // state is accepting or stuck, any other token iff its bytes walk from the state without meeting dead; the rest
 // become -inf.  At a stuck state EOS is written 0.0f, which overrides a min_tokens ban: no row is ever all -inf.
+//
+// A JSON-mode row (entry kGuideJson) walks the pushdown automaton instead: a non-EOS token keeps its bits iff its bytes
+// walk from the slot's (state, depth, stack) without dying.  EOS is 0.0f iff the row is stuck = no other token of the
+// GLOBAL vocabulary survives (always so at kJsonDone), else -inf.  Survival can depend on the stack below its top
+// ("}}" against "]}"), so there is no per-state flag: the rank that owns EOS, when none of its own columns survives,
+// scans the rest of the vocabulary here.  Every other rank's columns are right without the answer.
+DEV void json_mask_row(const GuideParams& p, int b, int slot) {
+  JsonState s0;
+  if (!json_load(p, slot, &s0)) return;  // dead: the row stays bit-identical
+  float* row = p.logits + (size_t)b * p.ld;
+  const int e = p.eos - p.vocab_offset;  // EOS's column here, if this rank owns it
+  const bool own_eos = p.eos >= 0 && p.eos < p.v_global && (unsigned)e < (unsigned)p.V;
+  int any = 0;
+  for (int v = threadIdx.x; v < p.V; v += kGuideThreads) {
+    const int g = v + p.vocab_offset;
+    if (g >= p.v_global) { row[v] = -INFINITY; continue; }
+    if (g == p.eos) continue;  // written below, once the row knows whether it is stuck
+    JsonState s = s0;
+    if (json_walk(p, s, g)) any = 1;
+    else row[v] = -INFINITY;
+  }
+  if (!own_eos) return;  // (block-uniform)
+  any = __syncthreads_or(any);
+  if (!any && s0.q != kJsonDone) {  // (block-uniform) the other shards' tokens: [0, vocab_offset) and [offset + V, v_global)
+    const int rest = p.vocab_offset + max(0, p.v_global - p.vocab_offset - p.V);
+    for (int i = threadIdx.x; i < rest && !any; i += kGuideThreads) {
+      const int g = i < p.vocab_offset ? i : i + p.V;
+      if (g >= p.v_global || g == p.eos) continue;
+      JsonState s = s0;
+      if (json_walk(p, s, g)) any = 1;
+    }
+    any = __syncthreads_or(any);
+  }
+  if (threadIdx.x == 0) row[e] = any ? -INFINITY : 0.0f;
+}
+
 __global__ void __launch_bounds__(kGuideThreads) sample_guide_mask_kernel(GuideParams p) {
   const int b = blockIdx.x;
   int slot, entry, state;
   if (!guide_row(p, b, &slot, &entry, &state)) return;
+  if (entry == kGuideJson) { json_mask_row(p, b, slot); return; }
   if ((unsigned)state >= (unsigned)kGuideStates) return;
   const unsigned short* tab = p.tab + (size_t)entry * kGuideStates * 256;
   const int flags = p.flags[(size_t)entry * kGuideStates + state];
@@ -354,6 +452,19 @@ __global__ void sample_guide_advance_kernel(int B, GuideParams p) {
   if (!guide_row(p, b, &slot, &entry, &state)) return;
   const int id = DSSE_IDX(p.ids[b], p.v_global, -1);
   if (id == p.eos) return;
+  if (entry == kGuideJson) {  // JSON mode: (state, depth, stack) move together; a dead walk leaves only state = dead
+    JsonState s;
+    int* w = p.json_state + slot;
+    if (json_load(p, slot, &s) && (unsigned)id < (unsigned)p.v_global && json_walk(p, s, id)) {
+      w[0] = s.q;
+      w[p.slots] = s.depth;
+      w[2 * (size_t)p.slots] = (int)(unsigned)s.stack;
+      w[3 * (size_t)p.slots] = (int)(unsigned)(s.stack >> 32);
+    } else {
+      w[0] = kGuideDead;
+    }
+    return;
+  }
   int next = kGuideDead;
   if ((unsigned)state < (unsigned)kGuideStates && (unsigned)id < (unsigned)p.v_global)
     next = guide_walk(p, p.tab + (size_t)entry * kGuideStates * 256, state, id);
@@ -676,7 +787,8 @@ extern "C" hipError_t dsse_sample_bias_ban(int B, float* logits, const dsse::Sam
 
 static bool guide_ok(const dsse::GuideParams* p) {
   return p->tok_bytes && p->tok_len && p->tab && p->flags && p->meta && p->slots >= 1 && p->pool >= 1 &&
-         p->pool <= dsse::kGuidePool && p->v_global >= 1;
+         p->pool <= dsse::kGuidePool && p->v_global >= 1 && !p->json_tab == !p->json_state &&
+         (!p->json_tab || (p->json_states > dsse::kJsonAfterArr && p->json_states <= dsse::kJsonStates));
 }
 
 // The stuck bits of pool entry p->entry's states [0, p->n_states).

@@ -47,6 +47,7 @@ std::string encode_request(const ChatRequest& r) {
   w.i32((int32_t)r.stop.size());
   for (auto& s : r.stop) w.str(s);
   w.str(r.guide);
+  w.u8(r.guide_json ? 1 : 0);
   return w.data();
 }
 
@@ -83,6 +84,7 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   for (int32_t i = 0; i < n && rd.good(); ++i) r->stop.push_back(rd.str());
   r->guide = rd.str();
   if (r->guide.size() > 8192) return false;
+  r->guide_json = rd.u8() != 0;
   return rd.good();
 }
 }  // namespace dpwire

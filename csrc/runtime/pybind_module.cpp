@@ -50,6 +50,7 @@ py::dict request_dict(const ChatRequest& r) {
   d["min_p"] = r.min_p;
   d["stop"] = r.stop;
   d["guide"] = r.guide;  // guided_regex, or guided_choice lowered to a pattern; "" = none
+  d["guide_json"] = r.guide_json;  // response_format json_object
   d["from_edge"] = r.from_edge;
   d["messages"] = r.messages_json;
   return d;

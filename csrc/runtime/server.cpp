@@ -326,6 +326,7 @@ bool parse_controls(const std::map<std::string, JsonValue>& o, ChatRequest& r, i
 // guided_regex / guided_choice of a /chat or /v1/chat/completions body.  Absent or JSON null = not given.  One of
 // them at most, never with ignore_eos (the guide ends a stream through EOS); the pattern must compile (guide.h), so a
 // bad one is a 400 carrying the compiler's message before the stream opens.  r.ignore_eos must already be set.
+// Also response_format (OpenAI's JSON mode), which is a guide of its own kind.
 bool parse_guide(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err) {
   auto field = [&](const char* k) -> const JsonValue* {
     auto it = o.find(k);
@@ -333,6 +334,29 @@ bool parse_guide(const std::map<std::string, JsonValue>& o, ChatRequest& r, std:
   };
   const JsonValue* re = field("guided_regex");
   const JsonValue* ch = field("guided_choice");
+  // response_format: absent, null or {"type":"text"} = nothing; {"type":"json_object"} = JSON mode (r.guide_json), which
+  // like a guide ends through EOS and excludes the other two; json_schema and anything else is refused, not ignored
+  if (const JsonValue* rf = field("response_format")) {
+    std::map<std::string, JsonValue> f;
+    auto ty = f.end();
+    if (rf->kind == JsonValue::kObject && parse_json_object(rf->raw, f)) ty = f.find("type");
+    if (ty == f.end() || ty->second.kind != JsonValue::kString) {
+      *err = "response_format must be an object with a string \"type\"";
+      return false;
+    }
+    const std::string& type = ty->second.str;
+    if (type == "json_object") {
+      if (re || ch) {
+        *err = "response_format json_object cannot be combined with guided_regex / guided_choice";
+        return false;
+      }
+      if (r.ignore_eos) { *err = "response_format json_object cannot be combined with ignore_eos"; return false; }
+      r.guide_json = true;
+    } else if (type != "text") {
+      *err = "response_format type '" + type + "' is not supported (text, json_object)";
+      return false;
+    }
+  }
   if (!re && !ch) return true;
   const char* name = re ? "guided_regex" : "guided_choice";
   if (re && ch) { *err = "guided_regex and guided_choice cannot both be given"; return false; }

@@ -90,6 +90,10 @@ class SamplingParams:
     # the candidates keeps the tokens whose bytes the DFA accepts from the slot's state, an advance pass after the
     # commit moves the state (sampler.hip sample_guide_mask_kernel / sample_guide_advance_kernel)
     guide: str | None = None
+    # JSON mode (response_format {"type": "json_object"}): the delivered text is a JSON object of the language J
+    # (docs/kernels.md, "Sampler"), or a viable prefix of one when max_tokens ends the stream first.  A pushdown walk
+    # inside the same two guide passes; it takes no pattern pool entry.  Mutually exclusive with `guide`.
+    json_object: bool = False
 
     def penalised(self) -> bool:
         return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
@@ -440,6 +444,11 @@ class LLMEngine:
         """Queue a request.  `rid` (a TP leader's request id, replayed on its followers) seeds the sampling RNG
         when the params carry no seed, so it must be the same on every rank of a TP group."""
         p = params or self.default_params
+        if p.json_object:
+            if p.guide is not None:
+                raise ValueError("json_object cannot be combined with a guide (guided_regex / guided_choice)")
+            if self.r.guide_pieces is None:
+                raise ValueError("JSON mode needs the vocabulary's pieces (ModelRunner.set_guide_vocab)")
         if p.guide is not None:
             self._guide_compiled(p.guide)  # (ValueError for a pattern the compiler rejects: nothing is queued)
             if self.r.guide_pieces is None:
@@ -810,6 +819,12 @@ class LLMEngine:
                 s.guide_entry = self._guide_acquire(s.params.guide)
                 r.set_guide(s.slot, s.guide_entry, ops.guide_walk(self._guide_compiled(s.params.guide)[0], 0, s.out_ids,
                                                                   *r.guide_host, r.guide_eos))
+            elif s.params.json_object:
+                # JSON mode holds no pool entry (it never waits for one, and _guide_release has nothing to give
+                # back): the slot gets the marker and the pushdown state after the tokens already published
+                r.enable_guides()
+                r.set_guide(s.slot, ops.JSON_ENTRY, ops.json_walk_ids(ops.JSON_START_STATE, s.out_ids, *r.guide_host,
+                                                                      r.guide_eos))
             else:
                 r.set_guide(s.slot, -1, 0)  # (a no-op until a guided request has been seen)
 

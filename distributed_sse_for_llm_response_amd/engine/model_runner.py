@@ -291,6 +291,10 @@ class ModelRunner:
         self.guide_eos = -1
         self.guide_pieces = None  # the vocabulary's pieces (set_guide_vocab): what the byte table is built from
         self.tok_bytes = self.tok_len = self.guide_tab = self.guide_flags = self.guide_meta = self.guide_host = None
+        # JSON mode (response_format json_object): the pushdown automaton's table and json_state = [lexical state |
+        # depth | stack bits 0..31 | stack bits 32..63] per slot, for the slots whose guide_meta pool index is
+        # ops.JSON_ENTRY; allocated with the rest by enable_guides
+        self.json_tab = self.json_state = None
         # ---- decode activations ----
         bf = dict(device=dev, dtype=torch.bfloat16)
         self.resid = torch.zeros(Bm, H, device=dev, dtype=torch.float32)
@@ -606,6 +610,9 @@ class ModelRunner:
         self.guide_flags = torch.zeros(ops.GUIDE_POOL, ops.GUIDE_STATES, device=dev, dtype=torch.int32)
         self.guide_meta = torch.zeros(2 * self.max_batch, device=dev, dtype=torch.int32)
         self.guide_meta[:self.max_batch] = -1
+        self.json_tab = torch.from_numpy(ops.json_table()[0].view(np.int16).copy()).to(dev)
+        self.json_state = torch.zeros(4 * self.max_batch, device=dev, dtype=torch.int32)
+        ops.guide_attach_json(self.guide_meta, self.json_tab, self.json_state)  # (they ride with guide_meta)
         self.guide_used = True
         self._capture_twins()
 
@@ -625,15 +632,21 @@ class ModelRunner:
         ops.guide_live(self.tok_bytes, self.tok_len, self.guide_tab, self.guide_flags, self.guide_meta, entry, n,
                        self.guide_eos)
 
-    def set_guide(self, slot: int, entry: int, state: int) -> None:
+    def set_guide(self, slot: int, entry: int, state) -> None:
         """A sequence takes `slot`: its pool entry (-1: no guide) and the DFA state after the tokens it has already
-        published, stream-ordered; from then on the advance pass owns the state."""
+        published, stream-ordered; from then on the advance pass owns the state.  JSON mode: entry = ops.JSON_ENTRY
+        and state = the (lexical state, depth, stack) after those tokens, which goes to the slot's json_state words
+        (zeroed for every other sequence)."""
         if not self.guide_used:
             return
-        m = torch.tensor([entry, state], dtype=torch.int32)
+        js = [0, 0, 0, 0]
+        if entry == ops.JSON_ENTRY:
+            js, state = ops.json_state_words(state), 0
+        m = torch.tensor([entry, state] + js, dtype=torch.int32)
         if self.device.type == "cuda":
             m = m.pin_memory()
-        self.guide_meta.view(2, -1)[:, slot].copy_(m, non_blocking=True)
+        self.guide_meta.view(2, -1)[:, slot].copy_(m[:2], non_blocking=True)
+        self.json_state.view(4, -1)[:, slot].copy_(m[2:], non_blocking=True)
 
     def _guide_mask(self, logits, active, row_slot) -> None:
         ops.guide_mask(logits, active, self.tok_bytes, self.tok_len, self.guide_tab, self.guide_flags, self.guide_meta,
@@ -916,6 +929,7 @@ class ModelRunner:
         arrays += [(self.lp_meta, 0)] if lp else []
         arrays += [(self.ctl_body, 0), (self.ctl_meta.view(4, -1), 1)] if ctl else []  # bias / ban records + columns
         arrays += [(self.guide_meta.view(2, -1), 1)] if guide else []  # the pool index and the device-owned DFA state
+        arrays += [(self.json_state.view(4, -1), 1)] if guide else []  # JSON mode's lexical state, depth and stack
         return arrays
 
     def decode(self, B: int) -> None:

@@ -299,6 +299,26 @@ def sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions,
 # guided decoding: DFA states per pattern / resident patterns / bytes per piece / the dead state (api.h)
 GUIDE_STATES, GUIDE_POOL, GUIDE_TOK_BYTES, GUIDE_DEAD = ref.GUIDE_STATES, ref.GUIDE_POOL, ref.GUIDE_TOK_BYTES, ref.GUIDE_DEAD
 guide_token_table, guide_walk = ref.guide_token_table, ref.guide_walk
+# JSON mode (response_format json_object): the guide_meta entry word of a JSON slot, the depth cap, the pushdown
+# automaton's table and its host walkers (bytes / the whole vocabulary / token ids); json_state int32 [4, slots]
+JSON_ENTRY, JSON_DEPTH, JSON_START, JSON_DONE = ref.JSON_ENTRY, ref.JSON_DEPTH, ref.JSON_START, ref.JSON_DONE
+JSON_START_STATE, JSON_DEAD_STATE = ref.JSON_START_STATE, ref.JSON_DEAD_STATE
+json_table, json_walk, json_walk_all, json_walk_ids = ref.json_table, ref.json_walk, ref.json_walk_all, ref.json_walk_ids
+json_state_words = ref.json_state_words
+
+
+def guide_attach_json(guide_meta, json_tab, json_state):
+    """JSON mode's two tensors travel with the guide_meta tensor they belong to (guide_mask / guide_advance keep their
+    signatures): json_tab int16 [n, 256] (json_table's bits) and json_state int32 [4 slots], on guide_meta's device.
+    Held as an attribute of this tensor object: a view or a copy of it does not carry them.  Returns guide_meta."""
+    if json_state.numel() != 2 * guide_meta.numel() or json_state.device != guide_meta.device:
+        raise ValueError("json_state must be [4 x slots] for guide_meta's slots, on its device")
+    guide_meta.json_mode = (json_tab, json_state)
+    return guide_meta
+
+
+def _json_of(guide_meta):
+    return getattr(guide_meta, "json_mode", (None, None))
 
 
 def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: int, n_states: int, eos: int = -1):
@@ -316,23 +336,27 @@ def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
     the candidates.  guide_meta int32 [2 slots] = pool index (-1 = off) | DFA state per slot; row b is slot
     row_slot[b] (else b).  Inactive rows, guide-off slots and dead states keep their logits bit for bit; otherwise a
     column stays iff its token's bytes walk from the state without meeting dead (EOS: iff accepting or stuck; 0.0 at a
-    stuck state), else -inf."""
+    stuck state), else -inf.  Where guide_meta carries JSON mode's tensors (guide_attach_json), a slot whose pool index
+    is JSON_ENTRY is masked by the pushdown walk of JSON mode, in the same launch; without them it counts as off."""
+    json_tab, json_state = _json_of(guide_meta)
     if _hip(logits):
         torch.ops.dsse.sample_guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta,
-                                         row_slot, vocab_offset, eos)
+                                         row_slot, vocab_offset, eos, json_tab, json_state)
     else:
         ref.guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, vocab_offset,
-                       eos)
+                       eos, json_tab, json_state)
 
 
 def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1):
     """After a commit: the guide state of row b's slot advances by the committed global id ids[b] (EOS: unchanged; a
-    dead walk or a token of length 0: dead)."""
+    dead walk or a token of length 0: dead).  JSON-mode slots move their json_state words (see guide_mask)."""
+    json_tab, json_state = _json_of(guide_meta)
     if _hip(guide_meta):
         torch.ops.dsse.sample_guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta,
-                                            row_slot, eos)
+                                            row_slot, eos, json_tab, json_state)
     else:
-        ref.guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, eos)
+        ref.guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, eos,
+                          json_tab, json_state)
 
 
 def sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,

@@ -537,11 +537,13 @@ def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: in
 
 
 def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, vocab_offset=0,
-               eos: int = -1):
+               eos: int = -1, json_tab=None, json_state=None):
     """In place on logits [B, V] (row b = slot row_slot[b], else b).  Inactive rows, slots with the guide off and
     slots in the dead state are not touched.  Otherwise column v (global id g = v + vocab_offset) becomes -inf unless
     g is allowed: EOS iff the state is accepting or stuck, another token iff its bytes walk from the state without
-    meeting dead; at a stuck state EOS becomes 0.0.  Allowed columns keep their bits."""
+    meeting dead; at a stuck state EOS becomes 0.0.  Allowed columns keep their bits.  A JSON-mode slot (entry
+    JSON_ENTRY; json_state given) walks the pushdown automaton from its (state, depth, stack) instead; EOS is 0.0 iff
+    no other token of the global vocabulary survives (always so at JSON_DONE), else -inf."""
     B, V = logits.shape
     slots = guide_meta.numel() // 2
     tb, tl = _guide_np(tok_bytes), _guide_np(tok_len)
@@ -551,6 +553,11 @@ def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
             continue
         slot = int(row_slot[b]) if row_slot is not None else b
         entry, state = int(guide_meta[slot]), int(guide_meta[slots + slot])
+        if entry == JSON_ENTRY and json_state is not None:
+            js = _json_state_of(json_state, slot)
+            if 0 <= js[0] < json_table()[0].shape[0] and 0 <= js[1] <= JSON_DEPTH:
+                _json_mask_row(logits[b], js, tb, tl, vocab_offset, eos)
+            continue
         if not 0 <= entry < guide_tab.shape[0] or not 0 <= state < GUIDE_STATES:
             continue
         flags = int(guide_flags[entry, state])
@@ -566,19 +573,232 @@ def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
             logits[b, e] = 0.0
 
 
-def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1):
+def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1,
+                  json_tab=None, json_state=None):
     """guide_meta's state of row b's slot = walk(state, bytes(ids[b])); EOS leaves it, a dead walk or a token of
-    length 0 makes it GUIDE_DEAD.  Inactive rows and slots with the guide off are skipped."""
+    length 0 makes it GUIDE_DEAD.  Inactive rows and slots with the guide off are skipped.  A JSON-mode slot moves
+    its json_state words instead (a dead walk writes the state word only)."""
     slots = guide_meta.numel() // 2
     for b in range(ids.numel()):
         if active is not None and not int(active[b]):
             continue
         slot = int(row_slot[b]) if row_slot is not None else b
         entry = int(guide_meta[slot])
+        if entry == JSON_ENTRY and json_state is not None and int(ids[b]) != eos:
+            js = json_walk_ids(_json_state_of(json_state, slot), [int(ids[b])], tok_bytes, tok_len, eos)
+            if js[0] == GUIDE_DEAD:
+                json_state.view(4, -1)[0, slot] = GUIDE_DEAD
+            else:
+                json_state.view(4, -1)[:, slot] = torch.tensor(json_state_words(js), dtype=torch.int32)
+            continue
         if not 0 <= entry < guide_tab.shape[0] or int(ids[b]) == eos:
             continue
         guide_meta[slots + slot] = guide_walk(_guide_tab_np(guide_tab, entry), int(guide_meta[slots + slot]),
                                               [int(ids[b])], tok_bytes, tok_len, eos)
+
+
+# ---- JSON mode (response_format json_object): the pushdown walk of the language J (docs/kernels.md, "Sampler") ----
+# A slot whose guide_meta entry word is JSON_ENTRY uses no pool entry; json_state int32 [4, slots] = [lexical state |
+# depth 0..JSON_DEPTH | stack bits 0..31 | stack bits 32..63] (state GUIDE_DEAD = dead; one stack bit per open
+# container, 0 = object, 1 = array, innermost at bit 0).  json_table() uint16 [n, 256]: entry = next state | action <<
+# 14, GUIDE_DEAD = no transition; action 1 / 2 pushes an object / array, 3 pops and the next state is what the pop
+# uncovers (JSON_DONE at depth 0, else JSON_AFTER_OBJ / JSON_AFTER_ARR).  The device walks the same table (api.h).
+JSON_ENTRY, JSON_DEPTH = -2, 64
+JSON_START, JSON_DONE, JSON_AFTER_OBJ, JSON_AFTER_ARR = 0, 1, 2, 3
+JSON_START_STATE, JSON_DEAD_STATE = (JSON_START, 0, 0), (GUIDE_DEAD, 0, 0)
+_JSON_PUSH_OBJ, _JSON_PUSH_ARR, _JSON_POP = 1 << 14, 2 << 14, 3 << 14
+_JSON_TABLE = None
+
+
+def json_table():
+    """The automaton, uint16 [n, 256], and (second value) the state numbers by name.  Lexical states are split by
+    context ("o": the innermost container is an object, "a": an array, "k": an object key), so a closing byte always
+    matches the stack's top bit and the byte after a number can be processed as the delimiter it is."""
+    global _JSON_TABLE
+    if _JSON_TABLE is not None:
+        return _JSON_TABLE
+    names = ["start", "done", "after_o", "after_a", "obj_open", "obj_key", "colon", "val_o", "arr_open", "val_a"]
+    for c in "oa":
+        names += [f"{n}_{c}" for n in ("minus", "zero", "int", "dot", "frac", "exp", "expsign", "expd",
+                                       "t", "tr", "tru", "f", "fa", "fal", "fals", "n", "nu", "nul")]
+    for c in "koa":
+        names += [f"{n}_{c}" for n in ("str", "esc", "u1", "u2", "u3", "u4", "t1", "t2", "t2e0", "t2ed", "t3", "t3f0",
+                                       "t3f4")]
+    S = {n: i for i, n in enumerate(names)}
+    assert (S["start"], S["done"], S["after_o"], S["after_a"]) == (JSON_START, JSON_DONE, JSON_AFTER_OBJ,
+                                                                   JSON_AFTER_ARR)
+    tab = np.full((len(names), 256), GUIDE_DEAD, dtype=np.uint16)
+
+    def put(state, chars, to):
+        for ch in chars:
+            tab[S[state], ch if isinstance(ch, int) else ord(ch)] = to if isinstance(to, int) else S[to]
+
+    ws, digits = " \t\n\r", "0123456789"
+    put("start", "{", S["obj_open"] | _JSON_PUSH_OBJ)
+    for st in ("after_o", "after_a", "obj_open", "obj_key", "colon", "val_o", "arr_open", "val_a"):
+        put(st, ws, st)
+    put("after_o", ",", "obj_key")
+    put("after_o", "}", _JSON_POP)
+    put("after_a", ",", "val_a")
+    put("after_a", "]", _JSON_POP)
+    put("obj_open", '"', "str_k")
+    put("obj_open", "}", _JSON_POP)
+    put("obj_key", '"', "str_k")
+    put("colon", ":", "val_o")
+    put("arr_open", "]", _JSON_POP)
+    for st, c in (("val_o", "o"), ("val_a", "a"), ("arr_open", "a")):  # a value starts
+        put(st, '"', f"str_{c}")
+        put(st, "{", S["obj_open"] | _JSON_PUSH_OBJ)
+        put(st, "[", S["arr_open"] | _JSON_PUSH_ARR)
+        put(st, "-", f"minus_{c}")
+        put(st, "0", f"zero_{c}")
+        put(st, "123456789", f"int_{c}")
+        for ch in "tfn":
+            put(st, ch, f"{ch}_{c}")
+    for c in "oa":
+        after = f"after_{c}"
+        put(f"minus_{c}", "0", f"zero_{c}")
+        put(f"minus_{c}", "123456789", f"int_{c}")
+        put(f"int_{c}", digits, f"int_{c}")
+        for st in (f"zero_{c}", f"int_{c}"):
+            put(st, ".", f"dot_{c}")
+            put(st, "eE", f"exp_{c}")
+        put(f"dot_{c}", digits, f"frac_{c}")
+        put(f"frac_{c}", digits, f"frac_{c}")
+        put(f"frac_{c}", "eE", f"exp_{c}")
+        put(f"exp_{c}", "+-", f"expsign_{c}")
+        put(f"exp_{c}", digits, f"expd_{c}")
+        put(f"expsign_{c}", digits, f"expd_{c}")
+        put(f"expd_{c}", digits, f"expd_{c}")
+        for st in (f"zero_{c}", f"int_{c}", f"frac_{c}", f"expd_{c}"):  # one byte of lookahead: the delimiter
+            for ch in ws + ",}]":
+                tab[S[st], ord(ch)] = tab[S[after], ord(ch)]
+        for word in ("true", "false", "null"):
+            for i in range(1, len(word)):
+                put(f"{word[:i]}_{c}", word[i], f"{word[:i + 1]}_{c}" if i + 1 < len(word) else after)
+    for c, closed in (("k", "colon"), ("o", "after_o"), ("a", "after_a")):
+        s = lambda n: f"{n}_{c}"  # noqa: E731
+        put(s("str"), range(0x20, 0x80), s("str"))
+        put(s("str"), '"', closed)
+        put(s("str"), "\\", s("esc"))
+        put(s("str"), range(0xC2, 0xE0), s("t1"))
+        put(s("str"), range(0xE0, 0xF0), s("t2"))
+        put(s("str"), [0xE0], s("t2e0"))  # no overlong three-byte forms
+        put(s("str"), [0xED], s("t2ed"))  # no encoded surrogates
+        put(s("str"), range(0xF1, 0xF4), s("t3"))
+        put(s("str"), [0xF0], s("t3f0"))  # no overlong four-byte forms
+        put(s("str"), [0xF4], s("t3f4"))  # nothing above U+10FFFF
+        put(s("esc"), '"\\/bfnrt', s("str"))
+        put(s("esc"), "u", s("u1"))
+        for a, b in (("u1", "u2"), ("u2", "u3"), ("u3", "u4"), ("u4", "str")):
+            put(s(a), digits + "abcdefABCDEF", s(b))
+        put(s("t1"), range(0x80, 0xC0), s("str"))
+        put(s("t2"), range(0x80, 0xC0), s("t1"))
+        put(s("t2e0"), range(0xA0, 0xC0), s("t1"))
+        put(s("t2ed"), range(0x80, 0xA0), s("t1"))
+        put(s("t3"), range(0x80, 0xC0), s("t2"))
+        put(s("t3f0"), range(0x90, 0xC0), s("t2"))
+        put(s("t3f4"), range(0x80, 0x90), s("t2"))
+    _JSON_TABLE = (tab, S)
+    return _JSON_TABLE
+
+
+def json_walk(data, state=JSON_START_STATE):
+    """The byte walker: the (state, depth, stack) after the bytes `data` from `state`; JSON_DEAD_STATE where the walk
+    dies (no transition, or a push at depth JSON_DEPTH).  The text so far is in J iff the state is JSON_DONE."""
+    tab = json_table()[0]
+    q, depth, stack = state
+    if not (0 <= q < tab.shape[0] and 0 <= depth <= JSON_DEPTH):
+        return JSON_DEAD_STATE
+    for byte in bytes(data):
+        e = int(tab[q, byte])
+        if e == GUIDE_DEAD:
+            return JSON_DEAD_STATE
+        act, q = e >> 14, e & 0x3FFF
+        if act == 3:
+            if depth < 1:
+                return JSON_DEAD_STATE
+            depth, stack = depth - 1, stack >> 1
+            q = JSON_DONE if depth == 0 else (JSON_AFTER_ARR if stack & 1 else JSON_AFTER_OBJ)
+        elif act:
+            if depth >= JSON_DEPTH:
+                return JSON_DEAD_STATE
+            depth, stack = depth + 1, ((stack << 1) | (act == 2)) & ((1 << 64) - 1)
+    return (q, depth, stack)
+
+
+def json_walk_all(state, tok_bytes, tok_len):
+    """json_walk of every token from `state`, vectorised over the vocabulary: (q, depth, stack) arrays, q = GUIDE_DEAD
+    where the token dies (length 0 or above GUIDE_TOK_BYTES included).  tok_bytes / tok_len: numpy uint8."""
+    tab = json_table()[0]
+    n = tok_len.shape[0]
+    q0, d0, s0 = state
+    q = np.full(n, q0, dtype=np.int64)
+    depth = np.full(n, d0, dtype=np.int64)
+    stack = np.full(n, s0, dtype=np.uint64)
+    q[(tok_len < 1) | (tok_len > GUIDE_TOK_BYTES)] = GUIDE_DEAD
+    if not (0 <= q0 < tab.shape[0] and 0 <= d0 <= JSON_DEPTH):
+        q[:] = GUIDE_DEAD
+    one = np.uint64(1)
+    for j in range(GUIDE_TOK_BYTES):
+        on = np.nonzero((tok_len > j) & (q != GUIDE_DEAD))[0]
+        if on.size == 0:
+            break
+        e = tab[q[on], tok_bytes[on, j]].astype(np.int64)
+        act, nq, d, s = e >> 14, e & 0x3FFF, depth[on], stack[on]
+        dead = e == GUIDE_DEAD
+        pop, push = (act == 3) & ~dead, ((act == 1) | (act == 2)) & ~dead
+        dead |= (pop & (d < 1)) | (push & (d >= JSON_DEPTH))
+        d = d - pop + push
+        s = np.where(pop, s >> one, np.where(push, (s << one) | (act == 2).astype(np.uint64), s))
+        nq = np.where(pop, np.where(d == 0, JSON_DONE, np.where((s & one) == one, JSON_AFTER_ARR, JSON_AFTER_OBJ)), nq)
+        nq[dead] = GUIDE_DEAD
+        q[on], depth[on], stack[on] = nq, d, s
+    return q, depth, stack
+
+
+def json_walk_ids(state, ids, tok_bytes, tok_len, eos: int = -1):
+    """Host walk over token ids: the (state, depth, stack) after the tokens `ids` from `state` (EOS leaves it unchanged;
+    a dead walk, an id outside the vocabulary or a token of length 0 makes it JSON_DEAD_STATE)."""
+    tb, tl = _guide_np(tok_bytes), _guide_np(tok_len)
+    for t in ids:
+        t = int(t)
+        if t == eos:
+            continue
+        if state[0] == GUIDE_DEAD or not (0 <= t < tl.shape[0] and 1 <= tl[t] <= GUIDE_TOK_BYTES):
+            return JSON_DEAD_STATE
+        state = json_walk(tb[t, :tl[t]].tobytes(), state)
+    return state if state[0] != GUIDE_DEAD else JSON_DEAD_STATE
+
+
+def json_state_words(state) -> list:
+    """(state, depth, stack) as json_state's four int32 words."""
+    q, depth, stack = state
+    w = [q, depth, stack & 0xFFFFFFFF, (stack >> 32) & 0xFFFFFFFF]
+    return [x - (1 << 32) if x >= (1 << 31) else x for x in w]
+
+
+def _json_state_of(json_state, slot: int):
+    w = [int(x) & 0xFFFFFFFF for x in json_state.view(4, -1)[:, slot].tolist()]
+    q = w[0] if w[0] < (1 << 31) else w[0] - (1 << 32)
+    d = w[1] if w[1] < (1 << 31) else w[1] - (1 << 32)
+    return (q, d, w[2] | (w[3] << 32))
+
+
+def _json_mask_row(row, state, tb, tl, vocab_offset: int, eos: int) -> None:
+    """One JSON-mode row of guide_mask (row: the float32 logits of this shard's V columns, in place)."""
+    V, Vg = row.shape[0], tl.shape[0]
+    alive = json_walk_all(state, tb, tl)[0] != GUIDE_DEAD  # over the GLOBAL vocabulary: the stuck decision needs it
+    if 0 <= eos < Vg:
+        alive[eos] = False
+    stuck = not alive.any()
+    ok = np.zeros(V, dtype=bool)
+    n = max(0, min(V, Vg - vocab_offset))
+    ok[:n] = alive[vocab_offset:vocab_offset + n]
+    row[torch.from_numpy(~ok)] = float("-inf")
+    e = eos - vocab_offset
+    if 0 <= eos < Vg and 0 <= e < n and stuck:
+        row[e] = 0.0
 
 
 def _hist_append(pen_meta, hist, slot: int, tok: int) -> None:

@@ -143,7 +143,8 @@ class EngineLoop(threading.Thread):
             min_tokens=int(req.get("min_tokens", 0)), stop_token_ids=tuple(int(t) for t in req.get("stop_token_ids") or ()),
             min_p=float(req.get("min_p", 0.0)), stop=tuple(req.get("stop") or ()),
             # guided_regex, or guided_choice lowered to a pattern (compiled once by the HTTP server to validate it)
-            guide=req.get("guide") or None)
+            guide=req.get("guide") or None,
+            json_object=bool(req.get("guide_json")))  # response_format {"type": "json_object"}
 
     def _watch_stop(self, req, prompt, params: SamplingParams) -> None:
         """A request with stop strings: its events pass through the matcher from now on."""

@@ -9,6 +9,10 @@
    graphs captured at startup, then the lazily captured twins (their one-off capture time is printed) with every
    stream unguided and with every stream guided by the 512-state pattern (the advance pass moves the states as the
    step samples).
+3. JSON mode (response_format json_object), in the same session: the mask pass alone with every row a JSON row at the
+   start state, inside a string (the most permissive state) and at depth 64, over the synthetic vocabulary with 64 of
+   its pieces replaced by JSON punctuation and fragments (the synthetic tokenizer has no braces); and the decode step
+   with every stream in JSON mode on the runner's own (brace-less) table: inside a string, and stuck at the start state.
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -23,6 +27,11 @@ sys.path.insert(0, ROOT)
 
 PATTERN = "[a-z ]{255}[a-z ]{255}[a-z ]"  # 512 states; every lower-case word of the vocabulary survives
 DIGITS = "[0-9]{255}[0-9]{255}[0-9]"      # 512 states; all but ten tokens die at their first byte
+JSON_PIECES = ["{", "}", "[", "]", '"', ":", ",", "\n", " ", "-", ".", "e", "E", "+", "true", "false", "null", '{"', '":',
+               '",', '"}', "}}", "]}", "[[", '":"', '": "', '", "', "},{", "{}", "[]", "\\n", '\\"', "\\u00e9", "é",
+               '":[', '":{', "}]", "]]", "],", "},", '"]', '"],', '":true', '":null', "\n  ", "\n    ", "1.5", "1e3", "-1",
+               "0.", '{"a":', '{"id":', '"name":', '"value":', "[1,", ",2", "2]", '["', '"]}', "}}}", "]]}", " :", " ,",
+               "\t"]
 
 
 def main():
@@ -119,6 +128,49 @@ def main():
     guide_all(-1)
     out["twins_all_unguided_with_meta_upload_us"] = guided_step_us(-1)
     print(json.dumps(out), flush=True)
+
+    # JSON mode: every row a pushdown row of the same two launches
+    assert len(JSON_PIECES) == 64
+    pieces = tok.pieces()
+    pieces[3:3 + len(JSON_PIECES)] = JSON_PIECES
+    jtb, jtl = (t.to(dev) for t in ops.guide_token_table(pieces, never={0, tok.eos_id}))
+    states = {"start": ops.JSON_START_STATE, "in_string": ops.json_walk(b'{"k":"'),
+              "depth_64": ops.json_walk(b'{"a":' * ops.JSON_DEPTH)}
+
+    def json_all(state):
+        m = torch.zeros(2 * B, dtype=torch.int32)
+        m[:B] = ops.JSON_ENTRY
+        r.guide_meta.copy_(m)
+        r.json_state.copy_(torch.tensor(ops.json_state_words(state), dtype=torch.int32).repeat_interleave(B))
+
+    def json_mask(tb, tl):
+        ops.guide_mask(x.copy_(x.clamp(min=-32)), None, tb, tl, r.guide_tab, r.guide_flags, r.guide_meta, None, 0,
+                       r.guide_eos)  # (r.guide_meta carries json_tab / json_state: ops.guide_attach_json)
+
+    jm = {"what": "JSON mask pass alone (each figure includes the row restore)", "rows": B, "V": cfg.vocab_size,
+          "json_pieces": len(JSON_PIECES), "row_restore_alone_us": timed_us(lambda: x.copy_(x.clamp(min=-32)))}
+    for name, state in states.items():
+        json_all(state)
+        jm[f"{name}_us"] = timed_us(lambda: json_mask(jtb, jtl))
+        jm[f"{name}_survivors"] = int((ops.json_walk_all(state, jtb.cpu().numpy(), jtl.cpu().numpy())[0]
+                                       != ops.GUIDE_DEAD).sum())
+    json_all(states["in_string"])
+    jm["in_string_brace_less_vocabulary_us"] = timed_us(lambda: json_mask(r.tok_bytes, r.tok_len))
+    print(json.dumps(jm), flush=True)
+
+    def json_step_us(state):
+        def fn():
+            json_all(state)  # (back to the same state: the advance pass moved it)
+            r.decode(B)
+        r.positions.fill_(a.ctx)
+        return timed_us(fn, warm=5, n=min(a.reps, 50))
+
+    js = {"what": "decode step, every stream in JSON mode (the runner's brace-less table)", "model": cfg.name,
+          "streams": B, "in_string_us": json_step_us(states["in_string"]),
+          "stuck_at_start_us": json_step_us(states["start"])}
+    guide_all(-1)
+    js["all_unguided_with_meta_upload_us"] = guided_step_us(-1)
+    print(json.dumps(js), flush=True)
 
 
 if __name__ == "__main__":
