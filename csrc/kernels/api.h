@@ -263,6 +263,11 @@ hipError_t dsse_silu_mul(int T, int F, const void* gu, void* h, hipStream_t st);
 hipError_t dsse_decode_prep(int B, const int* active, const int* positions, const int* block_tables,
                             int max_blocks, int num_blocks, int* slots, int* ctx_len, int* q_len, hipStream_t st);
 hipError_t dsse_ring_advance(int* counter, hipStream_t st);
+// KV page movers of the prefix cache's host tier (kv_pages.hip): gather = 1 copies the n pages listed in `blocks`
+// (device memory) into staging records [K layer 0 .. L-1 | V layer 0 .. L-1] of 2 L seg_bytes each; gather = 0 copies
+// the records back into the listed pages.  seg_bytes = Hkv * 4096 * itemsize (a multiple of 16); n = 0 launches nothing.
+hipError_t dsse_kv_pages(int gather, int n, void* k_cache, void* v_cache, const int* blocks, void* staging, int L,
+                         int num_blocks, unsigned seg_bytes, hipStream_t st);
 // TP all-reduce + residual + RMSNorm over IPC peer buffers (allreduce.hip)
 size_t dsse_ar_buffer_bytes(int rows, int H);
 hipError_t dsse_ar_alloc(size_t bytes, void** ptr, void* handle64, int* uncached);
@@ -281,6 +286,7 @@ hipError_t dsse_check_attention_prefill(int* out, int clear);
 hipError_t dsse_check_elementwise(int* out, int clear);
 hipError_t dsse_check_sampler(int* out, int clear);
 hipError_t dsse_check_gemm_tiled(int* out, int clear);
+hipError_t dsse_check_kv_pages(int* out, int clear);
 // Stamps build: bind the step-anatomy record buffer (common.h stamps::) of a kernel file; no-ops otherwise.
 hipError_t dsse_stamps_bind_gemm_stream(void* rec);
 hipError_t dsse_stamps_bind_elementwise(void* rec);

@@ -1579,6 +1579,53 @@ void ar_gather(const Tensor& cand, Tensor& out, const Tensor& peers, int64_t ran
                                 reinterpret_cast<unsigned int*>(err.data_ptr<int>()), cur_stream()));
 }
 
+// Host tier of the prefix cache (kv_pages.hip): whole KV pages <-> contiguous staging records.  Pure byte movers, so
+// any cache element type goes; K, V and staging must agree on it.  The block list's VALUES are validated by the Python
+// wrapper on the host (ops.kv_pages_gather / kv_pages_scatter: range, duplicates, staging capacity) -- it is built from
+// host lists, and reading it back here would be a device sync.
+void kv_pages(bool gather, const Tensor& k_cache, const Tensor& v_cache, const Tensor& blocks, const Tensor& staging) {
+  check_gpu(k_cache, "k_cache");
+  check_gpu(v_cache, "v_cache");
+  check_gpu(blocks, "blocks");
+  check_gpu(staging, "staging");
+  check_dtype(blocks, at::kInt, "blocks");
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 || k_cache.scalar_type() == at::kFloat8_e4m3fn,
+              "k_cache has dtype ", k_cache.scalar_type(), ", expected bfloat16 or float8_e4m3fn");
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type(), "v_cache has dtype ", v_cache.scalar_type(),
+              ", but k_cache has ", k_cache.scalar_type());
+  TORCH_CHECK(staging.scalar_type() == k_cache.scalar_type(), "staging has dtype ", staging.scalar_type(),
+              ", but the cache has ", k_cache.scalar_type());
+  TORCH_CHECK(k_cache.dim() == 5 && k_cache.size(3) == dsse::kBS && k_cache.size(4) == 128,
+              "k_cache must be [L, blocks, Hkv, 32, 128]");
+  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(3) == 128 && v_cache.size(4) == dsse::kBS &&
+                  v_cache.size(0) == k_cache.size(0) && v_cache.size(1) == k_cache.size(1) &&
+                  v_cache.size(2) == k_cache.size(2),
+              "v_cache must be [L, blocks, Hkv, 128, 32] with k_cache's L, blocks and Hkv");
+  TORCH_CHECK(k_cache.device() == v_cache.device() && k_cache.device() == staging.device() &&
+                  k_cache.device() == blocks.device(), "kv_pages: every tensor must be on the same device");
+  const int64_t L = k_cache.size(0), nb = k_cache.size(1), hkv = k_cache.size(2), n = blocks.numel();
+  const int64_t seg = hkv * dsse::kBS * 128 * (int64_t)k_cache.element_size();
+  TORCH_CHECK(L >= 1 && nb >= 1 && hkv >= 1 && nb <= INT_MAX && seg % 16 == 0 && seg <= UINT_MAX && 2 * L <= INT_MAX,
+              "kv_pages: unsupported cache shape");
+  TORCH_CHECK(blocks.dim() == 1, "blocks must be a 1-D int32 list of pages");
+  TORCH_CHECK(staging.dim() == 2 && staging.size(1) * (int64_t)staging.element_size() == 2 * L * seg,
+              "staging must be [records, bytes_per_block / itemsize] = [records, ", 2 * L * seg / k_cache.element_size(),
+              "]");
+  TORCH_CHECK(n <= staging.size(0), "blocks lists ", n, " pages but staging holds ", staging.size(0), " records");
+  TORCH_CHECK(n <= 65535, "blocks lists ", n, " pages; one launch moves 65535 at most");
+  for (const Tensor* t : {&k_cache, &v_cache, &staging})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "kv_pages: tensors must be 16-byte aligned");
+  if (n == 0) return;  // nothing is launched
+  DSSE_CHECK_HIP(dsse_kv_pages(gather ? 1 : 0, (int)n, k_cache.data_ptr(), v_cache.data_ptr(), blocks.data_ptr<int>(),
+                               staging.data_ptr(), (int)L, (int)nb, (unsigned)seg, cur_stream()));
+}
+void kv_pages_gather(const Tensor& k_cache, const Tensor& v_cache, const Tensor& blocks, Tensor& staging) {
+  kv_pages(true, k_cache, v_cache, blocks, staging);
+}
+void kv_pages_scatter(const Tensor& staging, const Tensor& blocks, Tensor& k_cache, Tensor& v_cache) {
+  kv_pages(false, k_cache, v_cache, blocks, staging);
+}
+
 int64_t kernels_abi_version() { return 16; }
 
 // The dispatch's choice for an (M, N, K) projection: (impl, tiled cfg, split, fix, model estimate in us) -- impl as
@@ -1611,19 +1658,19 @@ bool kernels_checked() { return true; }
 bool kernels_checked() { return false; }
 #endif
 
-// Checked build: [7, 4] int32 (line, value, bound, count) of the first out-of-range index per kernel file,
+// Checked build: [8, 4] int32 (line, value, bound, count) of the first out-of-range index per kernel file,
 // in the order of kCheckFiles; all zeros in the default build.  Synchronises the device.
-const char* const kCheckFiles[7] = {"gemm_skinny.hip", "gemm_stream.hip", "attention.hip", "attention_prefill.hip",
-                                    "elementwise.hip", "sampler.hip", "gemm_tiled.hip"};
+const char* const kCheckFiles[8] = {"gemm_skinny.hip", "gemm_stream.hip", "attention.hip", "attention_prefill.hip",
+                                    "elementwise.hip", "sampler.hip", "gemm_tiled.hip", "kv_pages.hip"};
 Tensor kernel_checks(bool clear) {
   using Reader = hipError_t (*)(int*, int);
-  static const Reader readers[7] = {dsse_check_gemm_skinny, dsse_check_gemm_stream, dsse_check_attention,
+  static const Reader readers[8] = {dsse_check_gemm_skinny, dsse_check_gemm_stream, dsse_check_attention,
                                     dsse_check_attention_prefill, dsse_check_elementwise, dsse_check_sampler,
-                                    dsse_check_gemm_tiled};
-  Tensor out = at::zeros({7, 4}, at::kInt);
+                                    dsse_check_gemm_tiled, dsse_check_kv_pages};
+  Tensor out = at::zeros({8, 4}, at::kInt);
   if (!kernels_checked()) return out;
   DSSE_CHECK_HIP(hipDeviceSynchronize());
-  for (int i = 0; i < 7; ++i) DSSE_CHECK_HIP(readers[i](out.data_ptr<int>() + 4 * i, clear ? 1 : 0));
+  for (int i = 0; i < 8; ++i) DSSE_CHECK_HIP(readers[i](out.data_ptr<int>() + 4 * i, clear ? 1 : 0));
   return out;
 }
 // Stamps build: step-anatomy records (common.h stamps::record) of the ring GEMMs and RMSNorms.  step_stamps_arm
@@ -1694,6 +1741,8 @@ TORCH_LIBRARY(dsse, m) {
   m.def("decode_prep(Tensor active, Tensor positions, Tensor block_tables, Tensor(a!) slots, "
         "Tensor(b!) ctx_len, Tensor(c!) q_len, int num_blocks=2147483647) -> ()");
   m.def("ring_advance(Tensor(a!) counter) -> ()");
+  m.def("kv_pages_gather(Tensor k_cache, Tensor v_cache, Tensor blocks, Tensor(a!) staging) -> ()");
+  m.def("kv_pages_scatter(Tensor staging, Tensor blocks, Tensor(a!) k_cache, Tensor(b!) v_cache) -> ()");
   m.def("paged_attention(int mode, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor q_start, Tensor q_len, Tensor ctx_len, Tensor work_seq, Tensor work_tile, Tensor(a!) out, "
         "Tensor(b!) part_o, Tensor(c!) part_ml, int part, int nparts, float k_scale=1.0, float v_scale=1.0) -> ()");
@@ -1768,6 +1817,8 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("silu_mul", &silu_mul);
   m.impl("decode_prep", &decode_prep);
   m.impl("ring_advance", &ring_advance);
+  m.impl("kv_pages_gather", &kv_pages_gather);
+  m.impl("kv_pages_scatter", &kv_pages_scatter);
   m.impl("paged_attention", &paged_attention);
   m.impl("flash_prefill_split", &flash_prefill_split);
   m.impl("qkv_attention_decode", &qkv_attention_decode);

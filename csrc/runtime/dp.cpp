@@ -377,9 +377,13 @@ void DpRouter::drain_loop(int w) {
       const int32_t nh = rd.good() ? rd.i32() : 0;
       for (int32_t k = 0; k < nh && rd.good(); ++k) metrics().engine_host_step_seconds.observe(rd.f64());
       const int32_t np = rd.good() ? rd.i32() : 0;
-      if (np == 3 && rd.good()) {
+      if ((np == 3 || np == 7) && rd.good()) {
         const double q = rd.f64(), h = rd.f64(), e = rd.f64();
         if (rd.good()) metrics().observe_prefix_cache(q, h, e);
+        if (np == 7) {  // the replica's host KV tier is on: spilled, restored, dropped pages and host-tier hit tokens
+          const double sp = rd.f64(), rs = rd.f64(), dr = rd.f64(), ht = rd.f64();
+          if (rd.good()) metrics().observe_kv_offload(sp, rs, dr, ht);
+        }
       }
       if (step_s > 0) metrics().engine_decode_step_seconds.observe(step_s);
       double batch = 0, kv = 0, active = 0;

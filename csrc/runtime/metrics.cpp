@@ -141,6 +141,17 @@ std::string Metrics::render() const {
     line(o, "engine_prefix_cache_evictions_total", "KV pages evicted from the prefix cache", "counter",
          engine_prefix_cache_evictions_total.get());
   }
+  if (kv_offload_on.load(std::memory_order_relaxed)) {
+    line(o, "engine_prefix_cache_offload_spilled_pages_total", "Evicted KV pages copied out to the host tier", "counter",
+         engine_prefix_cache_offload_spilled_pages_total.get());
+    line(o, "engine_prefix_cache_offload_restored_pages_total", "KV pages copied back from the host tier at admission",
+         "counter", engine_prefix_cache_offload_restored_pages_total.get());
+    line(o, "engine_prefix_cache_offload_dropped_pages_total",
+         "Evicted KV pages lost because no staging record or host slot was free", "counter",
+         engine_prefix_cache_offload_dropped_pages_total.get());
+    line(o, "engine_prefix_cache_offload_hit_tokens_total", "Prompt tokens served from the host tier", "counter",
+         engine_prefix_cache_offload_hit_tokens_total.get());
+  }
   line(o, "dp_workers_alive", "Data-parallel engine workers with a live heartbeat", "gauge", dp_workers_alive.get());
   line(o, "dp_requests_routed_total", "Chat requests routed to data-parallel engine workers", "counter",
        dp_requests_routed_total.get());

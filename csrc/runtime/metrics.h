@@ -91,6 +91,21 @@ class Metrics {
   Counter engine_prefix_cache_hits_total;
   Counter engine_prefix_cache_evictions_total;
   std::atomic<bool> prefix_cache_on{false};
+  // Host tier of the prefix cache (serve --kv-offload-gb): pages copied out to host memory at eviction, copied back at
+  // admission, evicted without a copy (no free staging record or host slot), and the prompt tokens the restored pages
+  // held.  Present in /metrics once an engine with the tier on has reported (observe_kv_offload).
+  Counter engine_prefix_cache_offload_spilled_pages_total;
+  Counter engine_prefix_cache_offload_restored_pages_total;
+  Counter engine_prefix_cache_offload_dropped_pages_total;
+  Counter engine_prefix_cache_offload_hit_tokens_total;
+  std::atomic<bool> kv_offload_on{false};
+  void observe_kv_offload(double spilled, double restored, double dropped, double hit_tokens) {
+    kv_offload_on.store(true, std::memory_order_relaxed);
+    if (spilled > 0) engine_prefix_cache_offload_spilled_pages_total.add(spilled);
+    if (restored > 0) engine_prefix_cache_offload_restored_pages_total.add(restored);
+    if (dropped > 0) engine_prefix_cache_offload_dropped_pages_total.add(dropped);
+    if (hit_tokens > 0) engine_prefix_cache_offload_hit_tokens_total.add(hit_tokens);
+  }
   void observe_prefix_cache(double queries, double hits, double evictions) {
     prefix_cache_on.store(true, std::memory_order_relaxed);
     if (queries > 0) engine_prefix_cache_queries_total.add(queries);

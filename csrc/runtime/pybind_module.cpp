@@ -464,6 +464,9 @@ PYBIND11_MODULE(_dsse_runtime, m) {
   m.def("observe_prefix_cache", [](double queries, double hits, double evictions) {
     metrics().observe_prefix_cache(queries, hits, evictions);
   }, py::arg("queries"), py::arg("hits"), py::arg("evictions"));
+  m.def("observe_kv_offload", [](double spilled, double restored, double dropped, double hit_tokens) {
+    metrics().observe_kv_offload(spilled, restored, dropped, hit_tokens);
+  });
   m.def("observe_itl", [](double s) { metrics().engine_itl_seconds.observe(s); });
   m.def("set_active_chats", [](double n) { metrics().active_chats.set(n); });
   m.def("uuid4", &uuid4);

@@ -51,8 +51,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from .kv_cache import PAGE, BlockAllocator, blocks_needed, page_hashes
-from .model_runner import PREFILL_GRAPH_SEQS, RING_SIZE, ModelRunner, PrefillSeq, batch_buckets, mixed_mode
+from .kv_cache import PAGE, BlockAllocator, HostPageStore, KVCache, blocks_needed, page_hashes
+from .model_runner import PREFILL_GRAPH_SEQS, RING_SIZE, KVOffload, ModelRunner, PrefillSeq, batch_buckets, mixed_mode
 
 
 @dataclass
@@ -333,7 +333,7 @@ class LLMEngine:
     def __init__(self, runner: ModelRunner, eos_id: int = 2, prefill_budget: int = 512,
                  idle_prefill_budget: int | None = None, default_params: SamplingParams | None = None,
                  pipeline_depth: int | None = None, max_pause_s: float = 30.0, deterministic: bool | None = None,
-                 prefix_cache: bool = False):
+                 prefix_cache: bool = False, kv_offload_pages: int = 0, offload_ring_pages: int | None = None):
         self.r = runner
         self.eos_id = eos_id
         # automatic prefix caching (off by default): full KV pages are indexed by the hash of the token prefix they
@@ -342,7 +342,26 @@ class LLMEngine:
         # not pages; drained steps are consumed by count), so block tables and start positions agree without
         # travelling.
         self.prefix_cache = bool(prefix_cache)
-        self.alloc = BlockAllocator(runner.kv.num_blocks, prefix_cache=self.prefix_cache)
+        # host tier behind the prefix cache (off by default): kv_offload_pages > 0 keeps that many evicted pages in
+        # (pinned) host memory; a later prompt whose hash chain runs past the resident pages continues into them, and
+        # the hit pages are copied back into fresh HBM pages at admission (_admit, _drain_spills; the device side and
+        # the ordering rules are model_runner.KVOffload's).  Not under TP: the followers' fixed-size step plan has no
+        # room for spill and restore lists.
+        self.offload = None
+        store = None
+        if kv_offload_pages:
+            if kv_offload_pages < 0:
+                raise ValueError("kv_offload_pages must be >= 0")
+            if not self.prefix_cache:
+                raise ValueError("the host KV tier (kv_offload_pages) needs prefix_cache=True: it holds evicted "
+                                 "prefix-cache pages")
+            if runner.comm.size > 1:
+                raise ValueError("the host KV tier (kv_offload_pages) is not supported with tensor parallelism")
+            kv = runner.kv
+            store = HostPageStore(kv_offload_pages, KVCache.bytes_per_block(kv.num_layers, kv.nkv, kv.dtype),
+                                  pinned=runner.device.type == "cuda")
+            self.offload = KVOffload(runner, store, offload_ring_pages)
+        self.alloc = BlockAllocator(runner.kv.num_blocks, prefix_cache=self.prefix_cache, host_store=store)
         # the runner's KV cache element type ("bf16" | "fp8_e4m3": ModelRunner(kv_cache_dtype=)); nothing the engine
         # schedules -- pages, block tables, slots, prefix hashes -- depends on it
         self.kv_cache_dtype = "fp8_e4m3" if runner.kv.is_fp8 else "bf16"
@@ -388,6 +407,11 @@ class LLMEngine:
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0,
                       # prefix caching: prompt tokens looked up / served from resident pages (admissions), pages evicted
                       "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0}
+        if self.offload is not None:
+            # host tier: pages copied out at eviction / evicted with their content already there / evicted with no
+            # free staging record or host slot (content lost) / copied back at admission, and the tokens those held
+            self.stats.update(offload_spilled_pages=0, offload_spill_skipped=0, offload_dropped_pages=0,
+                              offload_restored_pages=0, offload_hit_tokens=0)
         # admission keeps this many pages free for running sequences to grow into (vLLM's 1% watermark)
         self.watermark = max(1, runner.kv.num_blocks // 100)
         self._bt_new: list = []  # (sequence, page index, block) appended since the last upload
@@ -741,6 +765,33 @@ class LLMEngine:
             self.shared_write_violations += len(bad)
             raise AssertionError(f"prefix cache: step {self.step_no} would write shared KV pages (slot, block): {bad}")
 
+    def _drain_spills(self, reserve: int = 0) -> None:
+        """Copy the pages evicted since the last call out to the host tier.  Called after the allocations of a step
+        (and of an admission that restores) and BEFORE anything that writes the evicted blocks is enqueued, so the
+        gather reads the old content (KVOffload rule a).  Never waits: what exceeds the free staging records (less
+        `reserve`, kept for the caller's restore) or finds no host slot is dropped, least recently used first, and a
+        page whose content the store already holds is not copied again."""
+        off = self.offload
+        if off is None:
+            return
+        off.poll()
+        spills = self.alloc.take_spills()
+        if not spills:
+            return
+        st = self.alloc.host_store
+        todo = [(b, h) for b, h in spills if not st.has(h)]
+        self.stats["offload_spill_skipped"] += len(spills) - len(todo)
+        room = max(0, off.free_records() - reserve)
+        pairs = []
+        for b, h in todo[max(0, len(todo) - room):]:  # (the list is in eviction order: its head is dropped first)
+            slot = st.reserve(h)
+            if slot is not None:
+                pairs.append((b, slot))
+        self.stats["offload_dropped_pages"] += len(todo) - len(pairs)
+        self.stats["offload_spilled_pages"] += len(pairs)
+        if pairs:
+            off.spill(pairs)
+
     def _grow(self):
         """Before the decode step: every sequence in it needs the page its write position falls in."""
         need = [s for s in self.slots if s is not None and s.state == "decode" and not s.aborted
@@ -770,26 +821,54 @@ class LLMEngine:
             if s.params.guide is not None and s.params.guide not in self._guide_idx and \
                     all(n > 0 for n in self._guide_refs):
                 return  # its pattern is not resident and every pool entry is in use: it waits, as for KV pages
-            hits = []
+            hits, run, host = [], None, []
             if self.prefix_cache:
                 # the resident leading pages of the prompt minus its last token: at least one token is always
                 # prefilled, so the first token is sampled by the ordinary last-chunk path.  (Hashed once; looked up
                 # on every attempt while it waits: the index changes between steps.)
                 if not s.hashes:
                     s.hashes = page_hashes(s.prompt)
-                hits = self.alloc.lookup(s.hashes[:(len(s.prompt) - 1) // PAGE])
+                chain = s.hashes[:(len(s.prompt) - 1) // PAGE]
+                if self.offload is None:
+                    hits = self.alloc.lookup(chain)
+                else:
+                    # both tiers: run[i] is page i's resident block, or None for a page to copy back from the host
+                    # slot in `host` (at most as many as there are free staging records: a longer hit is cut there)
+                    self.offload.poll()
+                    run, host = self.alloc.lookup_tiers(chain, max_host=self.offload.free_records())
+                    hits = [b for b in run if b is not None]
+            # pages to allocate: everything that is not resident, the host-tier hits' new HBM pages included
             need = blocks_needed(len(s.prompt)) - len(hits)
             idle = not any(x is not None for x in self.slots)
             if need > self.alloc.num_free - (0 if idle else self.watermark):
                 if hits:
                     self.alloc.free(hits)  # it waits: the references go back (the pages stay indexed)
+                for _, slot in host:
+                    self.alloc.host_store.release(slot)
                 if idle and need + len(hits) > self.alloc.num_blocks:  # can never fit: fail it rather than wait forever
                     self.waiting.popleft()
                     self._finish(s, self._early, reason="length")
                     continue
                 return
             self.waiting.popleft()
-            s.blocks = hits + self.alloc.allocate(need)
+            if not host:
+                s.blocks = hits + self.alloc.allocate(need)
+            else:
+                # restore: the first new pages take the host-tier hits' places.  The allocation may have evicted
+                # pages (those very blocks among them): their gathers are enqueued first, then H2D + scatter, all
+                # before this prompt's first chunk -- the compute stream orders them (KVOffload rules a and d).
+                # The restored blocks are then published under their hashes like any prefilled page.
+                new = self.alloc.allocate(need)
+                self._drain_spills(reserve=len(host))
+                pairs = [(slot, new[j]) for j, (_, slot) in enumerate(host)]
+                self.offload.restore(pairs)
+                for (i, _), (_, b) in zip(host, pairs):
+                    run[i] = b
+                    self.alloc.publish(b, s.hashes[i])
+                s.blocks = run + new[len(host):]
+                hits = run
+                self.stats["offload_restored_pages"] += len(host)
+                self.stats["offload_hit_tokens"] += PAGE * len(host)
             s.slot = free
             s.state = "prefill"
             s.prefilled = PAGE * len(hits)  # its chunks start here: it writes private pages only
@@ -984,6 +1063,8 @@ class LLMEngine:
                 self._dirty_slots.add(s.slot)
         self._grow()
         self._admit()
+        # host tier: the pages this step's allocations evicted are copied out before the step that writes them
+        self._drain_spills()
         if not self.waiting:
             self._compact()
         t_a = time.perf_counter()

@@ -78,6 +78,98 @@ def page_hashes(tokens, prev: bytes = b"", first: int = 0) -> list:
     return out
 
 
+class HostPageStore:
+    """The prefix cache's second tier: evicted KV pages in host memory, indexed by the same content hashes.
+
+    One allocation of `capacity_pages` records of `bytes_per_block` bytes (pinned for a GPU engine, so the copies to
+    and from it are asynchronous; a plain tensor for the CPU engine), a hash -> slot index and an LRU order over the
+    slots that may be recycled.  A slot is
+
+    * ``free``     -- holds nothing;
+    * ``filling``  -- reserved for a page whose device-to-host copy is in flight: its hash is known (a second spill
+                      of the same content is refused) but ``find`` does not see it, so nothing reads half a page;
+    * ``ready``    -- holds a whole page; visible to ``find`` and, least recently used first, recyclable;
+    * ``reading``  -- ready, and the source of a host-to-device copy that has not completed (counted: several
+                      restores may read one slot): visible, never recycled.
+
+    The store only keeps books; the copies and their events belong to the runner (model_runner.KVOffload), which
+    calls ``commit`` / ``release`` when they have completed."""
+
+    FREE, FILLING, READY, READING = "free", "filling", "ready", "reading"
+
+    def __init__(self, capacity_pages: int, bytes_per_block: int, pinned: bool = False):
+        if capacity_pages < 1:
+            raise ValueError("the host KV tier needs room for at least one page")
+        self.capacity, self.bytes_per_block = int(capacity_pages), int(bytes_per_block)
+        self.buf = torch.empty(self.capacity, self.bytes_per_block, dtype=torch.uint8, pin_memory=bool(pinned))
+        self.state = [self.FREE] * self.capacity
+        self._free = list(range(self.capacity - 1, -1, -1))
+        self._slot_of: dict = {}   # hash -> slot (filling, ready or reading)
+        self._hash_of: dict = {}   # slot -> hash
+        self._readers = [0] * self.capacity
+        self._lru: OrderedDict = OrderedDict()  # ready slots, least recently used first
+        self.recycled = 0
+
+    def __len__(self) -> int:
+        return len(self._slot_of)
+
+    def has(self, h: bytes) -> bool:
+        """The hash holds a slot in any state (a page that is here, or on its way, is not spilled again)."""
+        return h in self._slot_of
+
+    def find(self, h: bytes):
+        """The slot of a whole page with this hash (ready or reading), or None."""
+        slot = self._slot_of.get(h)
+        return None if slot is None or self.state[slot] == self.FILLING else slot
+
+    def reserve(self, h: bytes):
+        """A ``filling`` slot for a page about to be copied in: a free one, else the least recently used ready one
+        (its content is dropped).  None when the hash already holds a slot or every slot is filling or being read."""
+        if h in self._slot_of:
+            return None
+        if self._free:
+            slot = self._free.pop()
+        elif self._lru:
+            slot, _ = self._lru.popitem(last=False)
+            del self._slot_of[self._hash_of.pop(slot)]
+            self.recycled += 1
+        else:
+            return None
+        self.state[slot] = self.FILLING
+        self._slot_of[h], self._hash_of[slot] = slot, h
+        return slot
+
+    def commit(self, slot: int) -> None:
+        """The copy into a filling slot has completed: the page is visible from now on."""
+        assert self.state[slot] == self.FILLING, (slot, self.state[slot])
+        self.state[slot] = self.READY
+        self._lru[slot] = None
+
+    def cancel(self, slot: int) -> None:
+        """A reserved slot whose copy was never issued goes back to the free list."""
+        assert self.state[slot] == self.FILLING, (slot, self.state[slot])
+        del self._slot_of[self._hash_of.pop(slot)]
+        self.state[slot] = self.FREE
+        self._free.append(slot)
+
+    def acquire(self, slot: int) -> None:
+        """A host-to-device copy will read this slot: it is not recycled until ``release``."""
+        assert self.state[slot] in (self.READY, self.READING), (slot, self.state[slot])
+        if self._readers[slot] == 0:
+            del self._lru[slot]
+            self.state[slot] = self.READING
+        self._readers[slot] += 1
+
+    def release(self, slot: int) -> None:
+        """One reader's copy has completed (or was never issued); the last one makes the slot recyclable again, as the
+        most recently used."""
+        assert self.state[slot] == self.READING and self._readers[slot] > 0, (slot, self.state[slot])
+        self._readers[slot] -= 1
+        if self._readers[slot] == 0:
+            self.state[slot] = self.READY
+            self._lru[slot] = None
+
+
 class BlockAllocator:
     """Free-list allocator of KV pages (host side; the device only sees block tables).
 
@@ -86,12 +178,21 @@ class BlockAllocator:
     evictable pages, where a later ``lookup`` can revive it; ``allocate`` takes plain free pages first and evicts
     from the pool's least recently used end only when they run out.  Only full pages are shared, and a shared page
     is never written again.  With the flag off nothing below the free list is touched: the same pages in the same
-    order as ever."""
+    order as ever.
 
-    def __init__(self, num_blocks: int, prefix_cache: bool = False):
+    host_store (a HostPageStore, with prefix_cache=True only) adds the host tier: an evicted page's (block, hash) goes
+    on a spill list that the engine drains (``take_spills``) and copies out before the page's new owner writes it, and
+    ``lookup_tiers`` continues a hash chain from the index into the store.  Which pages are handed out, and in which
+    order, does not depend on the store."""
+
+    def __init__(self, num_blocks: int, prefix_cache: bool = False, host_store: HostPageStore | None = None):
+        if host_store is not None and not prefix_cache:
+            raise ValueError("the host KV tier sits behind the prefix cache: it needs prefix_cache=True")
         self.num_blocks = num_blocks
         self._free = list(range(num_blocks - 1, -1, -1))
         self.prefix_cache = prefix_cache
+        self.host_store = host_store
+        self._spills: list = []  # (block, hash) of pages evicted since take_spills, least recently used first
         self.evictions = 0
         if prefix_cache:
             self._ref = [0] * num_blocks
@@ -117,8 +218,11 @@ class BlockAllocator:
                 b = self._free.pop()
             else:  # evict: the page leaves the index and is anybody's again
                 b, _ = self._lru.popitem(last=False)
-                del self._index[self._hash_of.pop(b)]
+                h = self._hash_of.pop(b)
+                del self._index[h]
                 self.evictions += 1
+                if self.host_store is not None:  # its bytes are still the page: the engine copies them out
+                    self._spills.append((b, h))
             self._ref[b] = 1
             out.append(b)
         return out
@@ -156,6 +260,37 @@ class BlockAllocator:
                 del self._lru[b]
             self._ref[b] += 1
         return out
+
+    def take_spills(self) -> list:
+        """(block, hash) of the pages evicted since the last call, in eviction order (least recently used first).  The
+        blocks already belong to their new owners: the caller must enqueue their copies before anything writes them."""
+        out, self._spills = self._spills, []
+        return out
+
+    def lookup_tiers(self, hashes, max_host: int | None = None) -> tuple:
+        """``lookup`` across both tiers: the longest leading run of `hashes` whose pages are resident in HBM or whole
+        in the host store (HBM first; the run stops at the first hash in neither, and before host page number
+        `max_host` + 1: the caller can restore only so many).  Returns (run, host): run[i] is the block of page i, or
+        None for a page to restore; host = [(i, slot)] for those, in order.  A reference is taken on each block, and
+        each host slot is acquired (``reading``): the caller gives them back with ``free`` / ``host_store.release``."""
+        st = self.host_store
+        run, host = [], []
+        for i, h in enumerate(hashes):
+            b = self._index.get(h)
+            if b is None:
+                slot = st.find(h) if st is not None else None
+                if slot is None or (max_host is not None and len(host) >= max_host):
+                    break
+                host.append((i, slot))
+            run.append(b)
+        for b in run:
+            if b is not None:
+                if self._ref[b] == 0:
+                    del self._lru[b]
+                self._ref[b] += 1
+        for _, slot in host:
+            st.acquire(slot)
+        return run, host
 
     def publish(self, block: int, h: bytes) -> bool:
         """Record the content hash of a full page whose 32 writes are all enqueued.  A hash that is already indexed

@@ -1421,3 +1421,142 @@ class _PrefillStatic:
 
     def upload_padding(self):
         self.upload([], self.tmax)
+
+
+# Device staging records of the host KV tier (KVOffload): what one engine step can spill plus restore.  64 pages are
+# 256 MiB of HBM for the full model in bf16 (128 MiB in fp8) and 2048 tokens of prefix per admission; pages evicted
+# beyond the free records in one step are dropped, and a host-tier hit longer than them is cut to what fits (the rest
+# of that prompt is prefilled as if it had missed).
+OFFLOAD_RING_PAGES = 64
+
+
+class KVOffload:
+    """Device side of the prefix cache's host tier: moves whole KV pages between the paged cache and a HostPageStore
+    through a ring of contiguous staging records on the device (ops.kv_pages_gather / kv_pages_scatter), with the
+    PCIe copies on a side stream behind events, as engine._Drain does for tokens.  The ops run eagerly on the compute
+    stream between graph replays; nothing here is captured.
+
+    Ordering rules (the engine holds (a) and the first half of (d), this class the rest):
+      (a) the gather of block b is enqueued before any kernel that writes b for its new owner: the engine drains the
+          allocator's spill list right after the allocations of a step, before the step (or a restore) is enqueued;
+      (b) a host slot is ``filling``, invisible to lookup, until its D2H event has completed (poll -> store.commit);
+      (c) a staging record is not reused before its copy is done: records return to the free set only in poll(),
+          once the event recorded behind their last use (a spill's D2H, a restore's scatter) has completed;
+      (d) H2D happens before the scatter (the compute stream waits for the copy's event), and the scatter before the
+          first step that reads the block (same stream, enqueued at admission, before the prompt's chunks);
+      (e) a host slot in ``reading`` is not recycled before its H2D event has completed: it is released in poll()
+          behind the restore's scatter event, which the H2D precedes.
+    Events are only ever polled (``query``): no call here waits on the device."""
+
+    def __init__(self, runner: ModelRunner, store, ring_pages: int | None = None):
+        kv = runner.kv
+        self.r, self.store = runner, store
+        self.R = int(ring_pages or OFFLOAD_RING_PAGES)
+        self.bytes_per_block = KVCache.bytes_per_block(kv.num_layers, kv.nkv, kv.dtype)
+        if self.R < 1:
+            raise ValueError("the host KV tier needs at least one staging record")
+        if store.bytes_per_block != self.bytes_per_block:
+            raise ValueError(f"host store records are {store.bytes_per_block} bytes, a KV page is {self.bytes_per_block}")
+        self.cuda = runner.device.type == "cuda"
+        self.staging = torch.zeros(self.R, self.bytes_per_block // kv.dtype.itemsize, dtype=kv.dtype,
+                                   device=runner.device)
+        self._busy = [False] * self.R
+        self._ops: list = []  # in flight: (kind, first record, count, host slots, event | None)
+        # block lists, one pinned row per possible first record: a row is rewritten only once its record is free again
+        self._idx = torch.zeros(self.R, self.R, dtype=torch.int32)
+        if self.cuda:
+            self._idx = self._idx.pin_memory()
+            self.stream = torch.cuda.Stream(runner.device)
+
+    def free_records(self) -> int:
+        return self._busy.count(False)
+
+    def _runs(self, n: int) -> list:
+        """Free records for n pages as contiguous runs [(first, count)] (a launch's records are one slice)."""
+        runs, i = [], 0
+        while n > 0 and i < self.R:
+            if self._busy[i]:
+                i += 1
+                continue
+            j = i
+            while j < self.R and not self._busy[j] and j - i < n:
+                self._busy[j] = True
+                j += 1
+            runs.append((i, j - i))
+            n -= j - i
+            i = j
+        assert n == 0, "more pages than free staging records (the caller asks free_records() first)"
+        return runs
+
+    def _rows(self, first: int, blocks: list):
+        row = self._idx[first, :len(blocks)]
+        row.copy_(torch.tensor(blocks, dtype=torch.int32))
+        return row
+
+    def spill(self, pairs: list) -> None:
+        """pairs = [(block, host slot)]: copy the blocks' pages into the (``filling``) host slots.  Enqueued now, on
+        the compute stream, so the pages are read before their new owners' kernels write them (rule a)."""
+        kv, at = self.r.kv, 0
+        for first, m in self._runs(len(pairs)):
+            part = pairs[at:at + m]
+            at += m
+            rec = self.staging[first:first + m]
+            ops.kv_pages_gather(kv.k, kv.v, self._rows(first, [b for b, _ in part]), rec)
+            ev = None
+            if self.cuda:
+                done = torch.cuda.Event()
+                done.record()
+                self.stream.wait_event(done)
+                with torch.cuda.stream(self.stream):
+                    for j, (_, slot) in enumerate(part):
+                        self.store.buf[slot].copy_(rec[j].view(torch.uint8), non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(self.stream)
+            else:
+                for j, (_, slot) in enumerate(part):
+                    self.store.buf[slot].copy_(rec[j].view(torch.uint8))
+            self._ops.append(("spill", first, m, [s for _, s in part], ev))
+
+    def restore(self, pairs: list) -> None:
+        """pairs = [(host slot, block)]: copy the (``reading``) host slots into the blocks, which the caller has just
+        allocated.  H2D on the side stream into free records, then one scatter per run on the compute stream behind
+        the copy's event (rule d)."""
+        kv, at = self.r.kv, 0
+        for first, m in self._runs(len(pairs)):
+            part = pairs[at:at + m]
+            at += m
+            rec = self.staging[first:first + m]
+            if self.cuda:
+                with torch.cuda.stream(self.stream):
+                    for j, (slot, _) in enumerate(part):
+                        rec[j].view(torch.uint8).copy_(self.store.buf[slot], non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record(self.stream)
+                torch.cuda.current_stream(self.r.device).wait_event(copied)
+            else:
+                for j, (slot, _) in enumerate(part):
+                    rec[j].view(torch.uint8).copy_(self.store.buf[slot])
+            ops.kv_pages_scatter(rec, self._rows(first, [b for _, b in part]), kv.k, kv.v)
+            ev = None
+            if self.cuda:
+                ev = torch.cuda.Event()
+                ev.record()
+            self._ops.append(("restore", first, m, [s for s, _ in part], ev))
+
+    def poll(self) -> None:
+        """Retire the operations whose events have completed (never waits): a spill's host slots become visible, a
+        restore's host slots recyclable, and their staging records free.  On the CPU every copy is done when issued;
+        it is still retired here, at the next poll, so both devices walk through the same states."""
+        if not self._ops:
+            return
+        live = []
+        for op in self._ops:
+            kind, first, m, slots, ev = op
+            if ev is not None and not ev.query():
+                live.append(op)
+                continue
+            for s in slots:
+                (self.store.commit if kind == "spill" else self.store.release)(s)
+            for i in range(first, first + m):
+                self._busy[i] = False
+        self._ops = live

@@ -433,6 +433,56 @@ def sample(logits, temperature, top_k, top_p, seeds, positions, active, next_ids
     sample_pick(cand.unsqueeze(0), active, next_ids, ring, ring_counter, positions_inc)
 
 
+def _kv_pages_args(k_cache, v_cache, blocks, staging, unique: bool):
+    """Validate a page list ON THE HOST before anything is launched (a wild copy on the GPU is a fault): every index in
+    [0, num_blocks), no duplicates for a scatter, no more pages than staging has records, and one element type for K,
+    V and staging.  `blocks`: a list of ints or a CPU int32 tensor (pinned: its upload is then asynchronous).  Returns
+    the list as an int32 tensor on the cache's device."""
+    if isinstance(blocks, torch.Tensor):
+        if blocks.is_cuda:
+            raise ValueError("blocks must be a host list or CPU tensor: its indices are validated before the launch")
+        if blocks.dtype != torch.int32 or blocks.dim() != 1:
+            raise ValueError(f"blocks must be a 1-D int32 tensor, got {blocks.dtype} {tuple(blocks.shape)}")
+        vals, host = blocks.tolist(), blocks
+    else:
+        vals = [int(b) for b in blocks]
+        host = None
+    if k_cache.dim() != 5 or v_cache.dim() != 5 or staging.dim() != 2:
+        raise ValueError("k_cache / v_cache must be the 5-D paged caches and staging [records, bytes_per_block / itemsize]")
+    if not (k_cache.dtype == v_cache.dtype == staging.dtype):
+        raise ValueError(f"staging dtype {staging.dtype} and cache dtypes {k_cache.dtype} / {v_cache.dtype} must agree")
+    num_blocks = k_cache.shape[1]
+    bad = [b for b in vals if not 0 <= b < num_blocks]
+    if bad:
+        raise ValueError(f"blocks: index {bad[0]} outside [0, {num_blocks})")
+    if unique and len(set(vals)) != len(vals):
+        raise ValueError("blocks: a scatter may name each page once (duplicate index)")
+    if len(vals) > staging.shape[0]:
+        raise ValueError(f"blocks: n = {len(vals)} pages exceed the staging capacity of {staging.shape[0]} records")
+    if host is None:
+        host = torch.tensor(vals, dtype=torch.int32)
+    return host.to(k_cache.device, non_blocking=True) if k_cache.is_cuda else host
+
+
+def kv_pages_gather(k_cache, v_cache, blocks, staging):
+    """staging[i] = page blocks[i] of the paged cache as one contiguous record [K layer 0 .. L-1 | V layer 0 .. L-1]
+    (host tier of the prefix cache; csrc/kernels/kv_pages.hip).  `blocks` is a host list, validated here."""
+    dev = _kv_pages_args(k_cache, v_cache, blocks, staging, unique=False)
+    if _hip(k_cache):
+        torch.ops.dsse.kv_pages_gather(k_cache, v_cache, dev, staging)
+    else:
+        ref.kv_pages_gather(k_cache, v_cache, dev, staging)
+
+
+def kv_pages_scatter(staging, blocks, k_cache, v_cache):
+    """The inverse of kv_pages_gather: page blocks[i] of the cache = staging[i]; every other page is untouched."""
+    dev = _kv_pages_args(k_cache, v_cache, blocks, staging, unique=True)
+    if _hip(k_cache):
+        torch.ops.dsse.kv_pages_scatter(staging, dev, k_cache, v_cache)
+    else:
+        ref.kv_pages_scatter(staging, dev, k_cache, v_cache)
+
+
 class KernelCheckError(RuntimeError):
     """An out-of-range device index caught by the checked kernel build."""
 

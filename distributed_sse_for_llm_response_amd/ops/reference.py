@@ -195,6 +195,33 @@ def ring_advance(counter):
     counter += 1
 
 
+# ---------------------------------------------------------------- KV page movers (host tier of the prefix cache)
+def _page_bytes(k_cache, v_cache, staging):
+    """uint8 views: the caches as [L, blocks, seg] and staging as [records, 2 (K | V), L, seg] (bytes only, so one
+    code path serves bf16 and fp8 caches)."""
+    L, nb = k_cache.shape[:2]
+    kb, vb = k_cache.view(torch.uint8).view(L, nb, -1), v_cache.view(torch.uint8).view(L, nb, -1)
+    return kb, vb, staging.view(torch.uint8).view(staging.shape[0], 2, L, kb.shape[2])
+
+
+def kv_pages_gather(k_cache, v_cache, blocks, staging):
+    """staging[i] = [K layer 0 .. L-1 | V layer 0 .. L-1] of page blocks[i]."""
+    kb, vb, sb = _page_bytes(k_cache, v_cache, staging)
+    idx, n = blocks.long(), blocks.numel()
+    if n:
+        sb[:n, 0] = kb[:, idx].transpose(0, 1)
+        sb[:n, 1] = vb[:, idx].transpose(0, 1)
+
+
+def kv_pages_scatter(staging, blocks, k_cache, v_cache):
+    """Page blocks[i] = staging[i] (the inverse of kv_pages_gather)."""
+    kb, vb, sb = _page_bytes(k_cache, v_cache, staging)
+    idx, n = blocks.long(), blocks.numel()
+    if n:
+        kb[:, idx] = sb[:n, 0].transpose(0, 1)
+        vb[:, idx] = sb[:n, 1].transpose(0, 1)
+
+
 # ---------------------------------------------------------------- attention
 def gather_kv(k_cache, v_cache, block_table, n, k_scale=1.0, v_scale=1.0):
     """Keys/values 0..n-1 of one sequence in natural order: ([n, Hkv, 128], [n, Hkv, 128]); an fp8 cache is

@@ -68,8 +68,27 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
     runner.set_guide_vocab(tok.pieces(), tok.eos_id)  # guided decoding constrains the text: the pieces' bytes
     engine = LLMEngine(runner, eos_id=tok.eos_id, prefill_budget=cfg.prefill_budget, max_pause_s=cfg.max_pause_s,
                        default_params=SamplingParams(temperature=cfg.temperature, max_tokens=cfg.max_tokens),
-                       prefix_cache=cfg.enable_prefix_caching)
+                       prefix_cache=cfg.enable_prefix_caching, kv_offload_pages=kv_offload_pages(cfg, runner))
+    if engine.offload is not None and (comm is None or comm.rank == 0):
+        st = engine.alloc.host_store
+        print(f"[engine] host KV tier: {st.capacity} pages of {st.bytes_per_block >> 10} KiB "
+              f"({st.capacity * st.bytes_per_block / 2**30:.2f} GiB {'pinned ' if runner.device.type == 'cuda' else ''}"
+              "host memory)", flush=True)
     return engine, tok
+
+
+def kv_offload_pages(cfg: ServeConfig, runner) -> int:
+    """Pages of the host KV tier for --kv-offload-gb / KV_OFFLOAD_GB (0 = off); start-up errors name the fix."""
+    cfg.validate()
+    if cfg.kv_offload_gb <= 0:
+        return 0
+    kv = runner.kv
+    per = KVCache.bytes_per_block(kv.num_layers, kv.nkv, kv.dtype)
+    pages = int(cfg.kv_offload_gb * 2**30) // per
+    if pages < 1:
+        raise ValueError(f"--kv-offload-gb {cfg.kv_offload_gb} holds less than one KV page ({per} bytes = "
+                         f"{per / 2**30:.6f} GiB): raise it to at least that, or set it to 0 to turn the host tier off")
+    return pages
 
 
 class EngineLoop(threading.Thread):
@@ -84,6 +103,7 @@ class EngineLoop(threading.Thread):
     pub_lock = threading.Lock()  # class default (a loop built without __init__); each loop sets its own
     stops = None                 # (likewise: no stop-string matching)
     _prefix_cache = False        # (likewise: no cached_tokens on the terminal events, no prefix-cache counters)
+    _offload = False             # (likewise: no host-tier counters)
 
     def __init__(self, runtime, engine: LLMEngine, tokenizer, cfg: ServeConfig):
         super().__init__(daemon=True, name="engine-loop")
@@ -103,6 +123,11 @@ class EngineLoop(threading.Thread):
         # samples do -- straight into the in-process runtime, or with a DP worker's stats message
         self._prefix_cache = bool(getattr(getattr(engine, "engine", engine), "prefix_cache", False))
         self._prefix_seen = [0, 0, 0]
+        # host KV tier: its counters travel the same way, and /metrics names them only when the tier is on
+        self._offload = getattr(getattr(engine, "engine", engine), "offload", None) is not None
+        self._offload_seen = [0, 0, 0, 0]
+        if self._offload and not self._remote:
+            rt.observe_kv_offload(0, 0, 0, 0)
         if self._prefix_cache and not self._remote:
             rt.observe_prefix_cache(0, 0, 0)  # /metrics shows the counters from the start
         self.faults = FaultPlan.from_env()
@@ -256,6 +281,10 @@ class EngineLoop(threading.Thread):
                 d = self._prefix_delta()
                 if any(d):
                     self._rt.observe_prefix_cache(*d)
+            if self._offload:
+                d = self._offload_delta()
+                if any(d):
+                    self._rt.observe_kv_offload(*d)
             return
         if host >= 0:
             self._host.append(host)
@@ -269,7 +298,7 @@ class EngineLoop(threading.Thread):
         self._host.clear()
         if self._prefix_cache:
             self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs,
-                            self._prefix_delta())
+                            self._prefix_delta() + (self._offload_delta() if self._offload else []))
         else:
             self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs)
 
@@ -279,6 +308,15 @@ class EngineLoop(threading.Thread):
         now = [st.get("prefix_queries", 0), st.get("prefix_hit_tokens", 0), st.get("prefix_evictions", 0)]
         d = [float(a - b) for a, b in zip(now, self._prefix_seen)]
         self._prefix_seen = now
+        return d
+
+    def _offload_delta(self) -> list:
+        """[spilled, restored, dropped (pages), host-tier hit tokens] of the engine's host KV tier since the last call."""
+        st = self.engine.stats
+        now = [st.get(k, 0) for k in ("offload_spilled_pages", "offload_restored_pages", "offload_dropped_pages",
+                                      "offload_hit_tokens")]
+        d = [float(a - b) for a, b in zip(now, self._offload_seen)]
+        self._offload_seen = now
         return d
 
     def _shutdown(self) -> bool:

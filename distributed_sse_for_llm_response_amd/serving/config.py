@@ -10,7 +10,8 @@ Flow control (new): FLOW_HIGH_WATER (bytes queued for every subscriber of a conv
   pauses; 0 = off), MAX_PAUSE_S (a paused stream resumes after this long regardless).
 Engine keys (new): TP, DP, DP_PREFIX, DP_WORKER_TIMEOUT_MS, MAX_MODEL_LEN, MAX_BATCH, KV_BLOCK (fixed 32), GPU_MEMORY_UTILIZATION,
   SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH, ENABLE_PREFIX_CACHING (default 0),
-  DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured), KV_CACHE_DTYPE (auto | bf16 | fp8 | fp8_e4m3; default auto = bf16).
+  DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured), KV_CACHE_DTYPE (auto | bf16 | fp8 | fp8_e4m3; default auto = bf16),
+  KV_OFFLOAD_GB (GiB of pinned host memory per engine process behind the prefix cache; default 0 = off).
 """
 from __future__ import annotations
 
@@ -90,6 +91,9 @@ class ServeConfig:
     # KV cache element type: auto = bf16 (128 KiB per token at TP = 1), fp8 = fp8_e4m3 (64 KiB per token, twice the
     # pages in the same budget); passed to every engine replica / TP rank
     kv_cache_dtype: str = "auto"
+    # host tier of the prefix cache: GiB of pinned host memory per engine process that keep evicted KV pages (0 = off;
+    # needs enable_prefix_caching, not available with tp > 1); passed to every engine replica
+    kv_offload_gb: float = 0.0
 
     @classmethod
     def from_env(cls) -> "ServeConfig":
@@ -135,6 +139,7 @@ class ServeConfig:
         c.enable_prefix_caching = _env("ENABLE_PREFIX_CACHING", c.enable_prefix_caching, bool)
         c.dp_prefix_affinity_slack = _env("DP_PREFIX_AFFINITY_SLACK", c.dp_prefix_affinity_slack, int)
         c.kv_cache_dtype = _env("KV_CACHE_DTYPE", c.kv_cache_dtype, parse_kv_cache_dtype)
+        c.kv_offload_gb = _env("KV_OFFLOAD_GB", c.kv_offload_gb, float)
         return c
 
     @classmethod
@@ -155,6 +160,21 @@ class ServeConfig:
             if v is not None:
                 setattr(self, f.name, v)
         self.kv_cache_dtype = parse_kv_cache_dtype(self.kv_cache_dtype)
+        return self.validate()
+
+    def validate(self) -> "ServeConfig":
+        """Start-up errors of option combinations, each naming the fix (the CLI calls it once flags and environment
+        are merged; build_engine calls it again for configs built in code)."""
+        if self.kv_offload_gb < 0:
+            raise ValueError(f"--kv-offload-gb / KV_OFFLOAD_GB must be >= 0 (0 = off), got {self.kv_offload_gb}")
+        if self.kv_offload_gb > 0:
+            if not self.enable_prefix_caching:
+                raise ValueError("--kv-offload-gb / KV_OFFLOAD_GB needs the prefix cache: add --enable-prefix-caching "
+                                 "(ENABLE_PREFIX_CACHING=1), or set it to 0")
+            if self.tp > 1:
+                raise ValueError(f"--kv-offload-gb / KV_OFFLOAD_GB is not supported with tensor parallelism (tp = "
+                                 f"{self.tp}): run with --tp 1 (data parallelism, --dp N, works: every replica has its "
+                                 "own host tier), or set it to 0")
         return self
 
     def to_json(self) -> str:
