@@ -482,13 +482,28 @@ def test_qkv_attention_decode_folded_key_split_waves(gpu, monkeypatch, kwv, M, p
     _folded_case(gpu, monkeypatch, "auto", M, part, kwv)
 
 
-def _folded_case(gpu, monkeypatch, cfg, M, part, kwv, nparts=None):
+# the newest key opens a page, follows its first key, closes a page: at the first page, a middle page and the first
+# page of a 128-key partition (the folded kernel scores that key with an fp32 dot and writes it itself)
+PAGE_EDGE_CTXS = [1, 2, 32, 65, 66, 96, 129, 130, 160, 385, 386, 416]
+
+
+@pytest.mark.parametrize("kwv", ["1", "2", "4", "8"])
+@pytest.mark.parametrize("part,nparts", [(128, None), (0, 4)])
+def test_qkv_attention_decode_folded_page_edge_contexts(gpu, monkeypatch, kwv, part, nparts):
+    """The folded path with the contexts set explicitly (_folded_case otherwise leaves (ctx - 1) % 32 to the seed)."""
+    ctxs = PAGE_EDGE_CTXS * 2 + [560]  # 25 rows; the last one is made inactive
+    _folded_case(gpu, monkeypatch, "auto", len(ctxs), part, kwv, nparts=nparts, ctxs=ctxs)
+
+
+def _folded_case(gpu, monkeypatch, cfg, M, part, kwv, nparts=None, ctxs=None):
     monkeypatch.setenv("DSSE_KERNEL_CFG", ops.kernel_cfg_env(**GEMM_CONFIGS[cfg]))
     if kwv is not None:
         monkeypatch.setenv("DSSE_KERNEL_CFG", ops.kernel_cfg_env(attn_kwv=kwv))
     nh, nkv, H = 32, 8, 1024
     g = torch.Generator().manual_seed(M * 31 + part)
-    ctxs = torch.randint(1, 700, (M,), generator=g).tolist()
+    drawn = torch.randint(1, 700, (M,), generator=g).tolist()
+    ctxs = drawn if ctxs is None else list(ctxs)
+    assert len(ctxs) == M
     kc, vc, bt, _, _ = _attn_setup(ctxs, [1] * M, hq=nh, hkv=nkv, gen=g)
     ctx = torch.tensor(ctxs, dtype=torch.int32)
     qlen = torch.ones(M, dtype=torch.int32)
