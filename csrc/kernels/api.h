@@ -180,8 +180,18 @@ struct LogprobParams {
 //     1 / 2 pushes an object / array bit (dead at depth kJsonDepth); action 3 pops, and the next state then comes from
 //     what the pop uncovers: kJsonDone at depth 0, else kJsonAfterObj / kJsonAfterArr by the new innermost bit.  The
 //     lexical states are split by context (in an object / in an array), so a closing byte always matches the top bit.
+//
+// Schema guides (guided_json / response_format json_schema) need more states than kGuideStates, so they live in a
+// second, wide class of the same shape and semantics:
+//   guide_tab_wide [kGuideWidePool, kGuideWideStates, 256] (uint16) / guide_flags_wide [kGuideWidePool,
+//     kGuideWideStates] (int32), allocated when the first schema guide arrives (until then both pointers are null
+//     and pool_wide is 0).  A slot whose guide_meta entry word lies in [kGuidePool, kGuidePool + pool_wide) uses
+//     wide entry word - kGuidePool; its state is valid below kGuideWideStates.  An entry word or a state outside
+//     its class's range is dead: the row and the state stay untouched.  One launch mixes rows of every kind.
 constexpr int kGuideStates = 512;
 constexpr int kGuidePool = 32;     // resident patterns (32 x 512 x 256 x 2 B = 8 MiB)
+constexpr int kGuideWideStates = 4096;
+constexpr int kGuideWidePool = 4;  // resident schema guides (4 x 4096 x 256 x 2 B = 8 MiB)
 constexpr int kGuideTokBytes = 32;
 constexpr int kGuideDead = 0xFFFF;
 constexpr int kGuideJson = -2;     // guide_meta entry word of a JSON-mode slot
@@ -204,11 +214,15 @@ struct GuideParams {
   // advance pass
   const int* ids;          // [B] committed (global) ids
   // live pass
-  int entry, n_states;     // the pool entry just uploaded and its used states
+  int entry, n_states;     // the entry word just uploaded (wide: kGuidePool + its wide entry) and its used states
   // JSON mode (both null: a kGuideJson slot is treated as guide off)
   const unsigned short* json_tab;  // [json_states, 256]
   int* json_state;                 // [4, slots]
   int json_states;
+  // the wide class (both null and pool_wide 0: an entry word at or above kGuidePool is treated as guide off)
+  const unsigned short* tab_wide;  // [pool_wide, kGuideWideStates, 256]
+  int* flags_wide;                 // [pool_wide, kGuideWideStates]
+  int pool_wide;
 };
 
 }  // namespace dsse

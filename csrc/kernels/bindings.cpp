@@ -1253,11 +1253,38 @@ void guide_json(dsse::GuideParams& p, const c10::optional<Tensor>& json_tab, con
   p.json_states = (int)json_tab->size(0);
 }
 
-// Once per table upload, on the stream, before first use: the stuck bits of pool entry `entry`'s first n_states states.
+// The wide class (schema guides): guide_tab_wide int16 (uint16 bits) [pool <= 4, 4096, 256] and guide_flags_wide int32
+// [pool, 4096], given together or not at all (without them an entry word at or above kGuidePool is guide off).
+void guide_wide(dsse::GuideParams& p, const c10::optional<Tensor>& tab_wide, const c10::optional<Tensor>& flags_wide) {
+  TORCH_CHECK(tab_wide.has_value() == flags_wide.has_value(), "guide_tab_wide and guide_flags_wide go together");
+  if (!tab_wide.has_value()) return;
+  check_gpu(*tab_wide, "guide_tab_wide");
+  check_dtype(*tab_wide, at::kShort, "guide_tab_wide");
+  check_gpu(*flags_wide, "guide_flags_wide");
+  check_dtype(*flags_wide, at::kInt, "guide_flags_wide");
+  TORCH_CHECK(tab_wide->dim() == 3 && tab_wide->is_contiguous() && tab_wide->size(0) >= 1 &&
+                  tab_wide->size(0) <= dsse::kGuideWidePool && tab_wide->size(1) == dsse::kGuideWideStates &&
+                  tab_wide->size(2) == 256, "guide_tab_wide must be a contiguous [pool <= 4, 4096, 256]");
+  TORCH_CHECK(flags_wide->dim() == 2 && flags_wide->is_contiguous() && flags_wide->size(0) == tab_wide->size(0) &&
+                  flags_wide->size(1) == dsse::kGuideWideStates, "guide_flags_wide must be a contiguous [pool, 4096]");
+  p.tab_wide = reinterpret_cast<const unsigned short*>(tab_wide->data_ptr<int16_t>());
+  p.flags_wide = flags_wide->data_ptr<int>();
+  p.pool_wide = (int)tab_wide->size(0);
+}
+
+// Once per table upload, on the stream, before first use: the stuck bits of the first n_states states of the entry
+// word `entry` (a narrow entry, or kGuidePool + a wide entry).
 void guide_live(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& guide_tab, Tensor& guide_flags,
-                const Tensor& guide_meta, int64_t entry, int64_t n_states, int64_t eos) {
+                const Tensor& guide_meta, int64_t entry, int64_t n_states, int64_t eos,
+                const c10::optional<Tensor>& tab_wide, const c10::optional<Tensor>& flags_wide) {
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
-  TORCH_CHECK(entry >= 0 && entry < p.pool && n_states >= 1 && n_states <= dsse::kGuideStates, "bad entry / n_states");
+  guide_wide(p, tab_wide, flags_wide);
+  if (entry >= dsse::kGuidePool) {
+    TORCH_CHECK(entry - dsse::kGuidePool < p.pool_wide && n_states >= 1 && n_states <= dsse::kGuideWideStates,
+                "bad wide entry / n_states");
+  } else {
+    TORCH_CHECK(entry >= 0 && entry < p.pool && n_states >= 1 && n_states <= dsse::kGuideStates, "bad entry / n_states");
+  }
   p.entry = (int)entry;
   p.n_states = (int)n_states;
   DSSE_CHECK_HIP(dsse_guide_live(&p, cur_stream()));
@@ -1267,9 +1294,11 @@ void guide_live(const Tensor& tok_bytes, const Tensor& tok_len, const Tensor& gu
 void sample_guide_mask(Tensor& logits, const c10::optional<Tensor>& active, const Tensor& tok_bytes,
                        const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
                        const Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t vocab_offset,
-                       int64_t eos, const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state) {
+                       int64_t eos, const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state,
+                       const c10::optional<Tensor>& tab_wide, const c10::optional<Tensor>& flags_wide) {
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
   guide_json(p, json_tab, json_state);
+  guide_wide(p, tab_wide, flags_wide);
   p.logits = bind_logits(p, logits, vocab_offset);
   const int B = (int)logits.size(0);
   bind_rows(p, active, row_slot, B, p.slots);
@@ -1280,13 +1309,15 @@ void sample_guide_mask(Tensor& logits, const c10::optional<Tensor>& active, cons
 void sample_guide_advance(const Tensor& ids, const c10::optional<Tensor>& active, const Tensor& tok_bytes,
                           const Tensor& tok_len, const Tensor& guide_tab, const Tensor& guide_flags,
                           Tensor& guide_meta, const c10::optional<Tensor>& row_slot, int64_t eos,
-                          const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state) {
+                          const c10::optional<Tensor>& json_tab, const c10::optional<Tensor>& json_state,
+                          const c10::optional<Tensor>& tab_wide, const c10::optional<Tensor>& flags_wide) {
   check_gpu(ids, "ids");
   check_dtype(ids, at::kInt, "ids");
   TORCH_CHECK(ids.is_contiguous() && ids.numel() <= INT32_MAX, "ids must be contiguous");
   const int B = (int)ids.numel();
   dsse::GuideParams p = guide_params(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, eos);
   guide_json(p, json_tab, json_state);
+  guide_wide(p, tab_wide, flags_wide);
   bind_rows(p, active, row_slot, B, p.slots);
   p.ids = ids.data_ptr<int>();
   DSSE_CHECK_HIP(dsse_sample_guide_advance(B, &p, cur_stream()));
@@ -1767,13 +1798,14 @@ TORCH_LIBRARY(dsse, m) {
         "Tensor positions, Tensor? active, Tensor(a!) cand, Tensor ctl_meta, Tensor? row_slot=None, "
         "int vocab_offset=0) -> ()");
   m.def("guide_live(Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, Tensor(a!) guide_flags, Tensor guide_meta, "
-        "int entry, int n_states, int eos) -> ()");
+        "int entry, int n_states, int eos, Tensor? guide_tab_wide=None, Tensor(b!)? guide_flags_wide=None) -> ()");
   m.def("sample_guide_mask(Tensor(a!) logits, Tensor? active, Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, "
         "Tensor guide_flags, Tensor guide_meta, Tensor? row_slot=None, int vocab_offset=0, int eos=-1, "
-        "Tensor? json_tab=None, Tensor? json_state=None) -> ()");
+        "Tensor? json_tab=None, Tensor? json_state=None, Tensor? guide_tab_wide=None, "
+        "Tensor? guide_flags_wide=None) -> ()");
   m.def("sample_guide_advance(Tensor ids, Tensor? active, Tensor tok_bytes, Tensor tok_len, Tensor guide_tab, "
         "Tensor guide_flags, Tensor(a!) guide_meta, Tensor? row_slot=None, int eos=-1, Tensor? json_tab=None, "
-        "Tensor(b!)? json_state=None) -> ()");
+        "Tensor(b!)? json_state=None, Tensor? guide_tab_wide=None, Tensor? guide_flags_wide=None) -> ()");
   m.def("sample_pick_hist(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring, "
         "Tensor? ring_counter, Tensor(c!)? positions_inc, Tensor pen_meta, Tensor(d!) hist, "
         "int vocab=2147483647) -> ()");

@@ -273,8 +273,9 @@ __global__ void __launch_bounds__(kCtlThreads) sample_bias_ban_kernel(float* __r
 // ---- guided decoding: DFA token masking (api.h GuideParams) ------------------------------------------------------
 // The walk of one token's bytes from `state`: the state reached, kGuideDead where a byte has no transition.  Length 0
 // (or above kGuideTokBytes) = a token no guide allows.  Table entries are read through the vector L1 / L2: a used
-// table is at most 256 KiB and the rows of the few states a step visits stay resident (profiles/r10/guided_decoding.md).
-DEV int guide_walk(const GuideParams& p, const unsigned short* __restrict__ tab, int state, int g) {
+// table is at most 256 KiB (a wide one 2 MiB) and the rows of the few states a step visits stay resident
+// (profiles/r10/guided_decoding.md, profiles/guided_json.md).  `bound` = the states of the table's class.
+DEV int guide_walk(const GuideParams& p, const unsigned short* __restrict__ tab, int bound, int state, int g) {
   const int len = p.tok_len[g];
   if (len < 1 || len > kGuideTokBytes) return kGuideDead;
   const uint4* src = reinterpret_cast<const uint4*>(p.tok_bytes + (size_t)g * kGuideTokBytes);
@@ -285,13 +286,28 @@ DEV int guide_walk(const GuideParams& p, const unsigned short* __restrict__ tab,
     if (j >= len) break;
     const int byte = (w[j >> 2] >> (8 * (j & 3))) & 0xff;
     state = tab[(size_t)state * 256 + byte];
-    if (state >= kGuideStates) return kGuideDead;  // dead (or, never written by the host, an entry out of range)
+    if (state >= bound) return kGuideDead;  // dead (or, never written by the host, an entry out of range)
   }
   return state;
 }
 
+// The table of one entry word: the narrow pool below kGuidePool, the wide pool (schema guides) from there on.
+struct GuideTable {
+  const unsigned short* tab;
+  int* flags;
+  int bound;  // states of the class: a state at or above it is dead
+};
+DEV GuideTable guide_table(const GuideParams& p, int entry) {
+  if (entry >= kGuidePool) {
+    const size_t e = (size_t)(entry - kGuidePool);
+    return {p.tab_wide + e * kGuideWideStates * 256, p.flags_wide + e * kGuideWideStates, kGuideWideStates};
+  }
+  return {p.tab + (size_t)entry * kGuideStates * 256, p.flags + (size_t)entry * kGuideStates, kGuideStates};
+}
+
 // The guide of row b: false = nothing to do (inactive row, guide off, dead state).  A JSON-mode slot comes back with
-// entry = kGuideJson and its lexical state (json_load reads the rest).
+// entry = kGuideJson and its lexical state (json_load reads the rest), a wide-pool slot with its entry word
+// (kGuidePool + the wide entry; off where no wide pool is given or the entry is outside it).
 DEV bool guide_row(const GuideParams& p, int b, int* slot_out, int* entry_out, int* state_out) {
   if (p.active && !p.active[b]) return false;
   const int slot = DSSE_IDX(p.row_slot ? p.row_slot[b] : b, p.slots, -1);
@@ -304,8 +320,13 @@ DEV bool guide_row(const GuideParams& p, int b, int* slot_out, int* entry_out, i
     *state_out = p.json_state[slot];
     return true;
   }
-  const int entry = DSSE_IDX(raw, p.pool, -1);
-  if ((unsigned)entry >= (unsigned)p.pool) return false;
+  int entry = raw;
+  if (raw >= kGuidePool) {
+    if (!p.tab_wide || raw - kGuidePool >= p.pool_wide) return false;
+  } else {
+    entry = DSSE_IDX(raw, p.pool, -1);
+    if ((unsigned)entry >= (unsigned)p.pool) return false;
+  }
   *slot_out = slot;
   *entry_out = entry;
   *state_out = p.meta[p.slots + slot];
@@ -367,16 +388,17 @@ DEV bool json_walk(const GuideParams& p, JsonState& s, int g) {
 constexpr int kGuideThreads = 1024;
 
 // Once per table upload, one workgroup per used state: bit 1 of its flag = no token of the global vocabulary other
-// than EOS survives from it (the same on every TP rank: the table walked is the global one).
+// than EOS survives from it (the same on every TP rank: the table walked is the global one).  p.entry is an entry
+// word: a wide entry runs up to kGuideWideStates workgroups.
 __global__ void __launch_bounds__(kGuideThreads) guide_live_kernel(GuideParams p) {
   const int s = blockIdx.x;
-  const unsigned short* tab = p.tab + (size_t)p.entry * kGuideStates * 256;
+  const GuideTable t = guide_table(p, p.entry);
   int any = 0;
   for (int g = threadIdx.x; g < p.v_global && !any; g += kGuideThreads)
-    if (g != p.eos && guide_walk(p, tab, s, g) != kGuideDead) any = 1;
+    if (g != p.eos && guide_walk(p, t.tab, t.bound, s, g) != kGuideDead) any = 1;
   any = __syncthreads_or(any);
   if (threadIdx.x == 0) {
-    int* f = p.flags + (size_t)p.entry * kGuideStates + s;
+    int* f = t.flags + s;
     *f = (*f & 1) | (any ? 0 : 2);
   }
 }
@@ -427,9 +449,9 @@ __global__ void __launch_bounds__(kGuideThreads) sample_guide_mask_kernel(GuideP
   int slot, entry, state;
   if (!guide_row(p, b, &slot, &entry, &state)) return;
   if (entry == kGuideJson) { json_mask_row(p, b, slot); return; }
-  if ((unsigned)state >= (unsigned)kGuideStates) return;
-  const unsigned short* tab = p.tab + (size_t)entry * kGuideStates * 256;
-  const int flags = p.flags[(size_t)entry * kGuideStates + state];
+  const GuideTable t = guide_table(p, entry);
+  if ((unsigned)state >= (unsigned)t.bound) return;
+  const int flags = t.flags[state];
   float* row = p.logits + (size_t)b * p.ld;
   for (int v = threadIdx.x; v < p.V; v += kGuideThreads) {
     const int g = v + p.vocab_offset;
@@ -437,7 +459,7 @@ __global__ void __launch_bounds__(kGuideThreads) sample_guide_mask_kernel(GuideP
     if (g == p.eos) {
       if (flags & 2) row[v] = 0.0f;
       else if (!(flags & 1)) row[v] = -INFINITY;
-    } else if (guide_walk(p, tab, state, g) == kGuideDead) {
+    } else if (guide_walk(p, t.tab, t.bound, state, g) == kGuideDead) {
       row[v] = -INFINITY;
     }
   }
@@ -466,8 +488,9 @@ __global__ void sample_guide_advance_kernel(int B, GuideParams p) {
     return;
   }
   int next = kGuideDead;
-  if ((unsigned)state < (unsigned)kGuideStates && (unsigned)id < (unsigned)p.v_global)
-    next = guide_walk(p, p.tab + (size_t)entry * kGuideStates * 256, state, id);
+  const GuideTable t = guide_table(p, entry);
+  if ((unsigned)state < (unsigned)t.bound && (unsigned)id < (unsigned)p.v_global)
+    next = guide_walk(p, t.tab, t.bound, state, id);
   p.meta[p.slots + slot] = next;
 }
 
@@ -788,12 +811,18 @@ extern "C" hipError_t dsse_sample_bias_ban(int B, float* logits, const dsse::Sam
 static bool guide_ok(const dsse::GuideParams* p) {
   return p->tok_bytes && p->tok_len && p->tab && p->flags && p->meta && p->slots >= 1 && p->pool >= 1 &&
          p->pool <= dsse::kGuidePool && p->v_global >= 1 && !p->json_tab == !p->json_state &&
-         (!p->json_tab || (p->json_states > dsse::kJsonAfterArr && p->json_states <= dsse::kJsonStates));
+         (!p->json_tab || (p->json_states > dsse::kJsonAfterArr && p->json_states <= dsse::kJsonStates)) &&
+         !p->tab_wide == !p->flags_wide && (p->tab_wide ? p->pool_wide >= 1 && p->pool_wide <= dsse::kGuideWidePool
+                                                        : p->pool_wide == 0);
 }
 
-// The stuck bits of pool entry p->entry's states [0, p->n_states).
+// The stuck bits of the states [0, p->n_states) of the entry word p->entry (narrow: [0, pool); wide: kGuidePool +
+// [0, pool_wide)).
 extern "C" hipError_t dsse_guide_live(const dsse::GuideParams* p, hipStream_t st) {
-  if (!guide_ok(p) || p->entry < 0 || p->entry >= p->pool || p->n_states < 1 || p->n_states > dsse::kGuideStates)
+  if (!guide_ok(p) || p->n_states < 1) return hipErrorInvalidValue;
+  const bool wide = p->entry >= dsse::kGuidePool;
+  if (wide ? p->entry - dsse::kGuidePool >= p->pool_wide || p->n_states > dsse::kGuideWideStates
+           : p->entry < 0 || p->entry >= p->pool || p->n_states > dsse::kGuideStates)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(dsse::guide_live_kernel, dim3(p->n_states), dim3(dsse::kGuideThreads), 0, st, *p);
   return hipGetLastError();

@@ -48,6 +48,7 @@ std::string encode_request(const ChatRequest& r) {
   for (auto& s : r.stop) w.str(s);
   w.str(r.guide);
   w.u8(r.guide_json ? 1 : 0);
+  w.u8(r.guide_schema ? 1 : 0);
   return w.data();
 }
 
@@ -85,6 +86,7 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   r->guide = rd.str();
   if (r->guide.size() > 8192) return false;
   r->guide_json = rd.u8() != 0;
+  r->guide_schema = rd.u8() != 0;
   return rd.good();
 }
 }  // namespace dpwire

@@ -51,6 +51,7 @@ py::dict request_dict(const ChatRequest& r) {
   d["stop"] = r.stop;
   d["guide"] = r.guide;  // guided_regex, or guided_choice lowered to a pattern; "" = none
   d["guide_json"] = r.guide_json;  // response_format json_object
+  d["guide_schema"] = r.guide_schema;  // `guide` is a lowered JSON Schema (guided_json / json_schema): the wide class
   d["from_edge"] = r.from_edge;
   d["messages"] = r.messages_json;
   return d;
@@ -479,6 +480,21 @@ PYBIND11_MODULE(_dsse_runtime, m) {
                           py::bytes(reinterpret_cast<const char*>(d.table.data()), d.table.size() * sizeof(uint16_t)),
                           py::bytes(reinterpret_cast<const char*>(d.accept.data()), d.accept.size()));
   }, py::arg("pattern"));
+  // the same under the schema guide's caps (guide.h compile_wide), and the schema lowering that feeds it
+  m.def("guide_compile_wide", [](const std::string& pattern) {
+    guide::Dfa d;
+    std::string err;
+    if (!guide::compile_wide(pattern, &d, &err)) throw py::value_error(err);
+    return py::make_tuple(d.n_states, py::bytes(reinterpret_cast<const char*>(d.table.data()), d.table.size() * 2),
+                          py::bytes(reinterpret_cast<const char*>(d.accept.data()), d.accept.size()));
+  }, py::arg("pattern"));
+  m.def("guide_schema_pattern", [](const std::string& schema) {
+    std::string pattern, err;
+    if (!guide::schema_pattern(schema, &pattern, &err)) throw py::value_error(err);
+    return pattern;
+  }, py::arg("schema"));
+  m.attr("GUIDE_WIDE_STATES") = guide::kGuideWideStates;
+  m.attr("GUIDE_SCHEMA_BYTES") = guide::kGuideSchemaBytes;
   m.def("guide_choice_pattern", &guide::choice_pattern, py::arg("choices"));
   m.attr("GUIDE_STATES") = guide::kGuideStates;
   m.attr("GUIDE_PATTERN_BYTES") = guide::kGuidePatternBytes;

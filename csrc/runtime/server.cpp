@@ -326,7 +326,9 @@ bool parse_controls(const std::map<std::string, JsonValue>& o, ChatRequest& r, i
 // guided_regex / guided_choice of a /chat or /v1/chat/completions body.  Absent or JSON null = not given.  One of
 // them at most, never with ignore_eos (the guide ends a stream through EOS); the pattern must compile (guide.h), so a
 // bad one is a 400 carrying the compiler's message before the stream opens.  r.ignore_eos must already be set.
-// Also response_format (OpenAI's JSON mode), which is a guide of its own kind.
+// Also response_format: OpenAI's JSON mode, which is a guide of its own kind, and json_schema, which like vLLM's
+// guided_json is lowered to a pattern (guide::schema_pattern) and compiled under the wide caps (r.guide_schema).  A
+// request takes one of guided_regex, guided_choice, guided_json and a non-text response_format at most.
 bool parse_guide(const std::map<std::string, JsonValue>& o, ChatRequest& r, std::string* err) {
   auto field = [&](const char* k) -> const JsonValue* {
     auto it = o.find(k);
@@ -334,8 +336,12 @@ bool parse_guide(const std::map<std::string, JsonValue>& o, ChatRequest& r, std:
   };
   const JsonValue* re = field("guided_regex");
   const JsonValue* ch = field("guided_choice");
+  const JsonValue* gj = field("guided_json");
+  std::string schema;        // the schema's JSON text, from guided_json or response_format json_schema
+  const char* name = nullptr;  // the field the guide came from
   // response_format: absent, null or {"type":"text"} = nothing; {"type":"json_object"} = JSON mode (r.guide_json), which
-  // like a guide ends through EOS and excludes the other two; json_schema and anything else is refused, not ignored
+  // like a guide ends through EOS and excludes the others; {"type":"json_schema","json_schema":{"schema":{...}}} = a
+  // schema guide (name, strict and description are accepted and unused); anything else is refused, not ignored
   if (const JsonValue* rf = field("response_format")) {
     std::map<std::string, JsonValue> f;
     auto ty = f.end();
@@ -350,18 +356,65 @@ bool parse_guide(const std::map<std::string, JsonValue>& o, ChatRequest& r, std:
         *err = "response_format json_object cannot be combined with guided_regex / guided_choice";
         return false;
       }
+      if (gj) { *err = "response_format json_object cannot be combined with guided_json"; return false; }
       if (r.ignore_eos) { *err = "response_format json_object cannot be combined with ignore_eos"; return false; }
       r.guide_json = true;
+    } else if (type == "json_schema") {
+      if (re || ch || gj) {
+        *err = "response_format json_schema cannot be combined with guided_regex / guided_choice / guided_json";
+        return false;
+      }
+      std::map<std::string, JsonValue> js;
+      auto sc = js.end();
+      auto it = f.find("json_schema");
+      if (it != f.end() && it->second.kind == JsonValue::kObject && parse_json_object(it->second.raw, js))
+        sc = js.find("schema");
+      if (sc == js.end() || sc->second.kind != JsonValue::kObject) {
+        *err = "response_format json_schema must carry an object \"json_schema\" with an object \"schema\"";
+        return false;
+      }
+      schema = sc->second.raw;
+      name = "response_format json_schema";
     } else if (type != "text") {
       *err = "response_format type '" + type + "' is not supported (text, json_object)";
       return false;
     }
   }
-  if (!re && !ch) return true;
-  const char* name = re ? "guided_regex" : "guided_choice";
-  if (re && ch) { *err = "guided_regex and guided_choice cannot both be given"; return false; }
+  if ((re != nullptr) + (ch != nullptr) + (gj != nullptr) > 1) {
+    *err = re && ch && !gj ? "guided_regex and guided_choice cannot both be given"
+                           : "guided_regex, guided_choice and guided_json: one at most";
+    return false;
+  }
+  if (gj) {
+    // an object, or a string that holds the schema's JSON text
+    if (gj->kind != JsonValue::kObject && gj->kind != JsonValue::kString) {
+      *err = "guided_json must be a JSON Schema: an object, or a string holding one";
+      return false;
+    }
+    schema = gj->kind == JsonValue::kObject ? gj->raw : gj->str;
+    name = "guided_json";
+  }
+  if (!re && !ch && !name) return true;
+  if (!name) name = re ? "guided_regex" : "guided_choice";
   if (r.ignore_eos) { *err = std::string(name) + " cannot be combined with ignore_eos"; return false; }
   std::string pattern;
+  if (!re && !ch) {
+    std::string serr;
+    guide::Dfa dfa;
+    if (!guide::schema_pattern(schema, &pattern, &serr) || !guide::compile_wide(pattern, &dfa, &serr)) {
+      // response_format json_schema with a schema that is just "any object" asks for what json_object gives: it
+      // keeps the answer such a request has always had, which names the type to use
+      const std::string_view tail = guide::kSchemaFreeFormRoot;
+      if (!gj && serr.size() >= tail.size() && serr.compare(serr.size() - tail.size(), tail.size(), tail) == 0)
+        *err = "response_format type 'json_schema' is not supported (text, json_object)";
+      else
+        *err = std::string(name) + ": " + serr;
+      return false;
+    }
+    r.guide = std::move(pattern);
+    r.guide_schema = true;
+    return true;
+  }
   if (re) {
     if (re->kind != JsonValue::kString || re->str.size() > 2048) {
       *err = "guided_regex must be a string of at most 2048 bytes";

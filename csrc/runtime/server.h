@@ -98,6 +98,9 @@ struct ChatRequest {
   // guided decoding: guided_regex (<= 2048 bytes), or guided_choice (1..64 distinct strings of 1..64 bytes) lowered
   // to an alternation of escaped literals; validated with guide::compile before the stream opens.  "" = none
   std::string guide;
+  // `guide` is a JSON Schema lowered by guide::schema_pattern (guided_json, or response_format json_schema with a
+  // schema of at most 8 KiB): it compiles with guide::compile_wide and takes a wide pool entry on the device
+  bool guide_schema = false;
   bool guide_json = false;  // response_format {"type":"json_object"}: JSON mode (never together with `guide`)
   bool from_edge = false;   // submitted by the edge /chat (a subscriber exists)
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON

@@ -90,6 +90,9 @@ class SamplingParams:
     # the candidates keeps the tokens whose bytes the DFA accepts from the slot's state, an advance pass after the
     # commit moves the state (sampler.hip sample_guide_mask_kernel / sample_guide_advance_kernel)
     guide: str | None = None
+    # the guide is a JSON Schema lowered to a pattern (guided_json / response_format json_schema; guide.h
+    # schema_pattern): it compiles under the wide caps (compile_wide) and lives in the device's wide pool
+    guide_schema: bool = False
     # JSON mode (response_format {"type": "json_object"}): the delivered text is a JSON object of the language J
     # (docs/kernels.md, "Sampler"), or a viable prefix of one when max_tokens ends the stream first.  A pushdown walk
     # inside the same two guide passes; it takes no pattern pool entry.  Mutually exclusive with `guide`.
@@ -396,12 +399,14 @@ class LLMEngine:
         # guided decoding: compiled patterns (pattern -> (table uint16 [n, 256], accept uint8 [n])), and the device
         # pool's entries: pattern -> index, references by live sequences per index, and the resident pattern per index
         # (an entry without references stays resident until another pattern needs it)
+        # Entries are entry words: [0, GUIDE_POOL) the narrow pool, [GUIDE_POOL, GUIDE_POOL + GUIDE_WIDE_POOL) the
+        # wide pool of schema guides; a key is (pattern, schema-derived), and each kind waits for its own pool.
         self._guide_dfa: dict = {}
         self._guide_idx: dict = {}
-        self._guide_refs = [0] * ops.GUIDE_POOL
-        self._guide_pat = [None] * ops.GUIDE_POOL
+        self._guide_refs = [0] * (ops.GUIDE_POOL + ops.GUIDE_WIDE_POOL)
+        self._guide_pat = [None] * (ops.GUIDE_POOL + ops.GUIDE_WIDE_POOL)
         self._guide_lru = 0
-        self._guide_used_at = [0] * ops.GUIDE_POOL
+        self._guide_used_at = [0] * (ops.GUIDE_POOL + ops.GUIDE_WIDE_POOL)
         self.ring_head = int(runner.ring_counter.item()) if runner.device.type == "cuda" else int(runner.ring_counter[0])
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0,
@@ -473,8 +478,10 @@ class LLMEngine:
                 raise ValueError("json_object cannot be combined with a guide (guided_regex / guided_choice)")
             if self.r.guide_pieces is None:
                 raise ValueError("JSON mode needs the vocabulary's pieces (ModelRunner.set_guide_vocab)")
+        if p.guide_schema and p.guide is None:
+            raise ValueError("guide_schema needs the lowered pattern in guide")
         if p.guide is not None:
-            self._guide_compiled(p.guide)  # (ValueError for a pattern the compiler rejects: nothing is queued)
+            self._guide_compiled(p.guide, p.guide_schema)  # (ValueError for a pattern the compiler rejects: nothing is queued)
             if self.r.guide_pieces is None:
                 raise ValueError("guided decoding needs the vocabulary's pieces (ModelRunner.set_guide_vocab)")
         max_prompt = self.r.max_model_len - 1
@@ -651,33 +658,40 @@ class LLMEngine:
         ids = ([] if p.ignore_eos else [int(self.eos_id)]) + [int(t) for t in p.stop_token_ids]
         return [t for t in dict.fromkeys(ids) if 0 <= t < V]
 
-    def _guide_compiled(self, pattern: str):
-        """(table, accept) of `pattern`, compiled once (the same compiler the HTTP routes validate with)."""
-        hit = self._guide_dfa.get(pattern)
+    def _guide_compiled(self, pattern: str, schema: bool = False):
+        """(table, accept) of `pattern`, compiled once (the same compiler the HTTP routes validate with; a
+        schema-derived pattern under the wide caps)."""
+        hit = self._guide_dfa.get((pattern, schema))
         if hit is None:
             from .. import runtime
 
-            n, tab, acc = runtime.load().guide_compile(pattern)
+            rt = runtime.load()
+            n, tab, acc = rt.guide_compile_wide(pattern) if schema else rt.guide_compile(pattern)
             hit = (np.frombuffer(tab, dtype=np.uint16).reshape(n, 256), np.frombuffer(acc, dtype=np.uint8))
             if len(self._guide_dfa) >= 4 * ops.GUIDE_POOL:  # bounded: drop the oldest
                 self._guide_dfa.pop(next(iter(self._guide_dfa)))
-            self._guide_dfa[pattern] = hit
+            self._guide_dfa[(pattern, schema)] = hit
         return hit
 
-    def _guide_acquire(self, pattern: str) -> int:
-        """A reference to the pool entry that holds `pattern`, uploading its table into a free entry (one without
-        references, the least recently used) when it is not resident; -1 = every entry is referenced: wait."""
-        e = self._guide_idx.get(pattern, -1)
+    @staticmethod
+    def _guide_pool(schema: bool) -> range:
+        """The entry words of a guide's pool."""
+        return range(ops.GUIDE_POOL, ops.GUIDE_POOL + ops.GUIDE_WIDE_POOL) if schema else range(ops.GUIDE_POOL)
+
+    def _guide_acquire(self, pattern: str, schema: bool = False) -> int:
+        """A reference to the pool entry that holds `pattern`, uploading its table into a free entry of its pool (one
+        without references, the least recently used) when it is not resident; -1 = every entry is referenced: wait."""
+        e = self._guide_idx.get((pattern, schema), -1)
         if e < 0:
-            free = [i for i in range(ops.GUIDE_POOL) if self._guide_refs[i] == 0]
+            free = [i for i in self._guide_pool(schema) if self._guide_refs[i] == 0]
             if not free:
                 return -1
             e = min(free, key=lambda i: (self._guide_pat[i] is not None, self._guide_used_at[i]))
             if self._guide_pat[e] is not None:
                 del self._guide_idx[self._guide_pat[e]]
-            tab, acc = self._guide_compiled(pattern)
+            tab, acc = self._guide_compiled(pattern, schema)
             self.r.upload_guide(e, tab, acc)  # (the first one allocates the pool and captures the graph twins)
-            self._guide_pat[e], self._guide_idx[pattern] = pattern, e
+            self._guide_pat[e], self._guide_idx[(pattern, schema)] = (pattern, schema), e
         self._guide_refs[e] += 1
         self._guide_lru += 1
         self._guide_used_at[e] = self._guide_lru
@@ -818,8 +832,8 @@ class LLMEngine:
                 max_new = max(1, min(s.params.max_tokens, r.max_model_len - s.orig_len, cap))
                 s.params = SamplingParams(**{**s.params.__dict__, "max_tokens": max_new,
                                              "min_tokens": max(0, min(int(s.params.min_tokens), max_new))})
-            if s.params.guide is not None and s.params.guide not in self._guide_idx and \
-                    all(n > 0 for n in self._guide_refs):
+            if s.params.guide is not None and (s.params.guide, s.params.guide_schema) not in self._guide_idx and \
+                    all(self._guide_refs[i] > 0 for i in self._guide_pool(s.params.guide_schema)):
                 return  # its pattern is not resident and every pool entry is in use: it waits, as for KV pages
             hits, run, host = [], None, []
             if self.prefix_cache:
@@ -895,9 +909,11 @@ class LLMEngine:
             if s.params.guide is not None:
                 # its pattern's pool entry, and the DFA state after the tokens it has already published (after a
                 # preemption the regenerated tokens continue the same match); the device advances it from here on
-                s.guide_entry = self._guide_acquire(s.params.guide)
-                r.set_guide(s.slot, s.guide_entry, ops.guide_walk(self._guide_compiled(s.params.guide)[0], 0, s.out_ids,
-                                                                  *r.guide_host, r.guide_eos))
+                wide = s.params.guide_schema
+                s.guide_entry = self._guide_acquire(s.params.guide, wide)
+                r.set_guide(s.slot, s.guide_entry,
+                            ops.guide_walk(self._guide_compiled(s.params.guide, wide)[0], 0, s.out_ids, *r.guide_host,
+                                           r.guide_eos, ops.GUIDE_WIDE_STATES if wide else ops.GUIDE_STATES))
             elif s.params.json_object:
                 # JSON mode holds no pool entry (it never waits for one, and _guide_release has nothing to give
                 # back): the slot gets the marker and the pushdown state after the tokens already published

@@ -291,6 +291,9 @@ class ModelRunner:
         self.guide_eos = -1
         self.guide_pieces = None  # the vocabulary's pieces (set_guide_vocab): what the byte table is built from
         self.tok_bytes = self.tok_len = self.guide_tab = self.guide_flags = self.guide_meta = self.guide_host = None
+        # the wide pool of schema guides (guided_json / response_format json_schema): allocated by the first schema
+        # guide (enable_wide_guides), entry words ops.GUIDE_POOL + e
+        self.guide_tab_wide = self.guide_flags_wide = None
         # JSON mode (response_format json_object): the pushdown automaton's table and json_state = [lexical state |
         # depth | stack bits 0..31 | stack bits 32..63] per slot, for the slots whose guide_meta pool index is
         # ops.JSON_ENTRY; allocated with the rest by enable_guides
@@ -616,19 +619,48 @@ class ModelRunner:
         self.guide_used = True
         self._capture_twins()
 
+    def enable_wide_guides(self) -> None:
+        """The first schema guide: allocate the wide pool (8 MiB, as large as the narrow one) and attach it to
+        guide_meta.  Graphs captured with the guide passes hold the launch records of before, whose wide pointers are
+        null, so they are dropped and the pass set in use is captured again, once; the pass set itself is the same."""
+        if self.guide_tab_wide is not None:
+            return
+        self.enable_guides()
+        dev = self.device
+        self.guide_tab_wide = torch.full((ops.GUIDE_WIDE_POOL, ops.GUIDE_WIDE_STATES, 256), -1, device=dev,
+                                         dtype=torch.int16)
+        self.guide_flags_wide = torch.zeros(ops.GUIDE_WIDE_POOL, ops.GUIDE_WIDE_STATES, device=dev, dtype=torch.int32)
+        ops.guide_attach_wide(self.guide_meta, self.guide_tab_wide, self.guide_flags_wide)
+        for key, twins in self._twins.items():
+            if key[3]:
+                for d in twins:
+                    d.clear()
+        if self._captured_key[3]:  # capture() ran with the guides on: its graphs are stale too, twins replace them
+            self._captured_key = (None, None, None, True)
+        self._capture_twins()
+
     def upload_guide(self, entry: int, table: np.ndarray, accept: np.ndarray) -> None:
         """Pattern table uint16 [n, 256] (n <= 512) and its accepting flags become pool entry `entry`, stream-ordered
-        after every step already enqueued; then the live pass marks its stuck states."""
-        self.enable_guides()
+        after every step already enqueued; then the live pass marks its stuck states.  entry >= ops.GUIDE_POOL: a
+        schema guide's table (n <= 4096) becomes wide entry entry - ops.GUIDE_POOL."""
         n = int(table.shape[0])
-        if not (1 <= n <= ops.GUIDE_STATES and table.shape[1] == 256 and 0 <= entry < ops.GUIDE_POOL):
-            raise ValueError("guide table must be [1..512, 256]")
+        if entry >= ops.GUIDE_POOL:
+            if not (1 <= n <= ops.GUIDE_WIDE_STATES and table.shape[1] == 256 and
+                    entry < ops.GUIDE_POOL + ops.GUIDE_WIDE_POOL):
+                raise ValueError("wide guide table must be [1..4096, 256]")
+            self.enable_wide_guides()
+            tabs, flgs, e = self.guide_tab_wide, self.guide_flags_wide, entry - ops.GUIDE_POOL
+        else:
+            if not (1 <= n <= ops.GUIDE_STATES and table.shape[1] == 256 and 0 <= entry):
+                raise ValueError("guide table must be [1..512, 256]")
+            self.enable_guides()
+            tabs, flgs, e = self.guide_tab, self.guide_flags, entry
         tab = torch.from_numpy(np.array(table, dtype=np.uint16).view(np.int16))
         flg = torch.from_numpy(np.ascontiguousarray(accept, dtype=np.int32) & 1)
         if self.device.type == "cuda":
             tab, flg = tab.pin_memory(), flg.pin_memory()
-        self.guide_tab[entry, :n].copy_(tab, non_blocking=True)
-        self.guide_flags[entry, :n].copy_(flg, non_blocking=True)
+        tabs[e, :n].copy_(tab, non_blocking=True)
+        flgs[e, :n].copy_(flg, non_blocking=True)
         ops.guide_live(self.tok_bytes, self.tok_len, self.guide_tab, self.guide_flags, self.guide_meta, entry, n,
                        self.guide_eos)
 

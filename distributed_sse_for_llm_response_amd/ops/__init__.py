@@ -299,6 +299,8 @@ def sample_candidates_min_p(logits, temperature, top_k, top_p, seeds, positions,
 # guided decoding: DFA states per pattern / resident patterns / bytes per piece / the dead state (api.h)
 GUIDE_STATES, GUIDE_POOL, GUIDE_TOK_BYTES, GUIDE_DEAD = ref.GUIDE_STATES, ref.GUIDE_POOL, ref.GUIDE_TOK_BYTES, ref.GUIDE_DEAD
 guide_token_table, guide_walk = ref.guide_token_table, ref.guide_walk
+# the wide class of schema guides (guided_json / response_format json_schema): states per table / resident tables
+GUIDE_WIDE_STATES, GUIDE_WIDE_POOL = ref.GUIDE_WIDE_STATES, ref.GUIDE_WIDE_POOL
 # JSON mode (response_format json_object): the guide_meta entry word of a JSON slot, the depth cap, the pushdown
 # automaton's table and its host walkers (bytes / the whole vocabulary / token ids); json_state int32 [4, slots]
 JSON_ENTRY, JSON_DEPTH, JSON_START, JSON_DONE = ref.JSON_ENTRY, ref.JSON_DEPTH, ref.JSON_START, ref.JSON_DONE
@@ -321,13 +323,37 @@ def _json_of(guide_meta):
     return getattr(guide_meta, "json_mode", (None, None))
 
 
+def guide_attach_wide(guide_meta, tab_wide, flags_wide):
+    """The wide pool of schema guides travels with guide_meta as JSON mode's tensors do: tab_wide int16 [pool <=
+    GUIDE_WIDE_POOL, GUIDE_WIDE_STATES, 256] and flags_wide int32 [pool, GUIDE_WIDE_STATES], on guide_meta's device.
+    A slot whose entry word is GUIDE_POOL + e then uses wide entry e; without them such a slot counts as off.
+    Returns guide_meta."""
+    if tab_wide.dim() != 3 or tuple(tab_wide.shape[1:]) != (GUIDE_WIDE_STATES, 256) or \
+            not 1 <= tab_wide.shape[0] <= GUIDE_WIDE_POOL or tab_wide.dtype != torch.int16 or \
+            tuple(flags_wide.shape) != (tab_wide.shape[0], GUIDE_WIDE_STATES) or flags_wide.dtype != torch.int32 or \
+            tab_wide.device != guide_meta.device or flags_wide.device != guide_meta.device:
+        raise ValueError("the wide pool must be int16 [pool <= 4, 4096, 256] and int32 [pool, 4096] on guide_meta's device")
+    guide_meta.wide_pool = (tab_wide, flags_wide)
+    return guide_meta
+
+
+def _wide_of(guide_meta):
+    return getattr(guide_meta, "wide_pool", (None, None))
+
+
 def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: int, n_states: int, eos: int = -1):
     """Once per table upload, stream-ordered before first use: bit 1 (stuck) of guide_flags[entry, s], s < n_states =
-    no token of the global vocabulary other than EOS survives from state s."""
+    no token of the global vocabulary other than EOS survives from state s.  entry >= GUIDE_POOL: wide entry entry -
+    GUIDE_POOL of the pool attached to guide_meta (guide_attach_wide), n_states <= GUIDE_WIDE_STATES."""
+    tab_wide, flags_wide = _wide_of(guide_meta)
+    if entry >= GUIDE_POOL and (tab_wide is None or entry - GUIDE_POOL >= tab_wide.shape[0]):
+        raise ValueError("guide_live: a wide entry needs the wide pool (guide_attach_wide)")
     if _hip(guide_tab):
-        torch.ops.dsse.guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry, n_states, eos)
+        torch.ops.dsse.guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry, n_states, eos,
+                                  tab_wide, flags_wide)
     else:
-        ref.guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry, n_states, eos)
+        ref.guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry, n_states, eos, tab_wide,
+                       flags_wide)
 
 
 def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, vocab_offset=0,
@@ -337,26 +363,30 @@ def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
     row_slot[b] (else b).  Inactive rows, guide-off slots and dead states keep their logits bit for bit; otherwise a
     column stays iff its token's bytes walk from the state without meeting dead (EOS: iff accepting or stuck; 0.0 at a
     stuck state), else -inf.  Where guide_meta carries JSON mode's tensors (guide_attach_json), a slot whose pool index
-    is JSON_ENTRY is masked by the pushdown walk of JSON mode, in the same launch; without them it counts as off."""
+    is JSON_ENTRY is masked by the pushdown walk of JSON mode, in the same launch; without them it counts as off.
+    Likewise a slot whose pool index is GUIDE_POOL + e walks wide entry e of the pool attached with guide_attach_wide
+    (states below GUIDE_WIDE_STATES)."""
     json_tab, json_state = _json_of(guide_meta)
+    tab_wide, flags_wide = _wide_of(guide_meta)
     if _hip(logits):
         torch.ops.dsse.sample_guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta,
-                                         row_slot, vocab_offset, eos, json_tab, json_state)
+                                         row_slot, vocab_offset, eos, json_tab, json_state, tab_wide, flags_wide)
     else:
         ref.guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, vocab_offset,
-                       eos, json_tab, json_state)
+                       eos, json_tab, json_state, tab_wide, flags_wide)
 
 
 def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1):
     """After a commit: the guide state of row b's slot advances by the committed global id ids[b] (EOS: unchanged; a
     dead walk or a token of length 0: dead).  JSON-mode slots move their json_state words (see guide_mask)."""
     json_tab, json_state = _json_of(guide_meta)
+    tab_wide, flags_wide = _wide_of(guide_meta)
     if _hip(guide_meta):
         torch.ops.dsse.sample_guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta,
-                                            row_slot, eos, json_tab, json_state)
+                                            row_slot, eos, json_tab, json_state, tab_wide, flags_wide)
     else:
         ref.guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot, eos,
-                          json_tab, json_state)
+                          json_tab, json_state, tab_wide, flags_wide)
 
 
 def sample_pick_hist(cand_all, active, next_ids, ring, ring_counter, positions_inc, pen_meta, hist,

@@ -494,6 +494,10 @@ def sample_bias_ban(logits, active, ctl_meta, ctl_body, positions, row_slot=None
 # allowed under a guide); guide_tab int16 (uint16 bits) [pool, GUIDE_STATES, 256], GUIDE_DEAD = dead; guide_flags int32
 # [pool, GUIDE_STATES]: bit 0 accepting, bit 1 stuck; guide_meta int32 [2 slots] = pool index (-1 = off) | state.
 GUIDE_STATES, GUIDE_POOL, GUIDE_TOK_BYTES, GUIDE_DEAD = 512, 32, 32, 0xFFFF
+# The wide class (schema guides): guide_tab_wide int16 [pool <= GUIDE_WIDE_POOL, GUIDE_WIDE_STATES, 256] and
+# guide_flags_wide int32 [pool, GUIDE_WIDE_STATES]; a guide_meta entry word in [GUIDE_POOL, GUIDE_POOL + pool) uses
+# wide entry word - GUIDE_POOL, and its state is valid below GUIDE_WIDE_STATES.
+GUIDE_WIDE_STATES, GUIDE_WIDE_POOL = 4096, 4
 
 
 def guide_token_table(pieces, never=()):
@@ -515,26 +519,27 @@ def _guide_np(t):
     return t.detach().cpu().contiguous().numpy()
 
 
-def _guide_walk_all(tab, state: int, tok_bytes, tok_len):
+def _guide_walk_all(tab, state: int, tok_bytes, tok_len, bound: int = GUIDE_STATES):
     """The state every token reaches from `state` (GUIDE_DEAD: none), vectorised over the vocabulary.  tab: uint16
-    [GUIDE_STATES, 256]."""
+    [bound, 256], bound = the states of the table's class."""
     st = np.full(tok_len.shape[0], state, dtype=np.int64)
     st[(tok_len < 1) | (tok_len > GUIDE_TOK_BYTES)] = GUIDE_DEAD
-    if not 0 <= state < GUIDE_STATES:
+    if not 0 <= state < bound:
         st[:] = GUIDE_DEAD
     for j in range(GUIDE_TOK_BYTES):
         on = (tok_len > j) & (st != GUIDE_DEAD)
         if not on.any():
             break
         nxt = tab[st[on], tok_bytes[on, j]].astype(np.int64)
-        nxt[nxt >= GUIDE_STATES] = GUIDE_DEAD
+        nxt[nxt >= bound] = GUIDE_DEAD
         st[on] = nxt
     return st
 
 
-def guide_walk(table, state: int, ids, tok_bytes, tok_len, eos: int = -1) -> int:
+def guide_walk(table, state: int, ids, tok_bytes, tok_len, eos: int = -1, bound: int = GUIDE_STATES) -> int:
     """Host walk: the DFA state after the tokens `ids` from `state` (EOS leaves it unchanged; a dead walk, an id
-    outside the vocabulary or a token of length 0 makes it GUIDE_DEAD).  table: uint16 [n_states, 256]."""
+    outside the vocabulary or a token of length 0 makes it GUIDE_DEAD).  table: uint16 [n_states, 256]; bound = the
+    states of its class (GUIDE_WIDE_STATES for a schema guide)."""
     table, tb, tl = np.asarray(table), _guide_np(tok_bytes), _guide_np(tok_len)
     for t in ids:
         t = int(t)
@@ -544,7 +549,7 @@ def guide_walk(table, state: int, ids, tok_bytes, tok_len, eos: int = -1) -> int
             return GUIDE_DEAD
         for byte in tb[t, :tl[t]]:
             state = int(table[state, byte])
-            if state >= min(GUIDE_STATES, table.shape[0]):
+            if state >= min(bound, table.shape[0]):
                 return GUIDE_DEAD
     return state
 
@@ -553,24 +558,37 @@ def _guide_tab_np(guide_tab, entry: int):
     return _guide_np(guide_tab[entry]).view(np.uint16)
 
 
-def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: int, n_states: int, eos: int = -1):
-    """Bit 1 of guide_flags[entry, s] for s < n_states: no token of the vocabulary other than EOS survives from s."""
+def _guide_class(guide_tab, guide_flags, entry: int, tab_wide, flags_wide):
+    """(table pool, flags pool, index, state bound) of an entry word; None = outside both pools (guide off)."""
+    if 0 <= entry < guide_tab.shape[0]:
+        return guide_tab, guide_flags, entry, GUIDE_STATES
+    if tab_wide is not None and 0 <= entry - GUIDE_POOL < tab_wide.shape[0]:
+        return tab_wide, flags_wide, entry - GUIDE_POOL, GUIDE_WIDE_STATES
+    return None
+
+
+def guide_live(tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, entry: int, n_states: int, eos: int = -1,
+               tab_wide=None, flags_wide=None):
+    """Bit 1 of the flag of state s < n_states of the entry word `entry` (a narrow entry, or GUIDE_POOL + a wide
+    one): no token of the vocabulary other than EOS survives from s."""
+    guide_tab, guide_flags, entry, bound = _guide_class(guide_tab, guide_flags, entry, tab_wide, flags_wide)
     tab, tb, tl = _guide_tab_np(guide_tab, entry), _guide_np(tok_bytes), _guide_np(tok_len)
     for s in range(n_states):
-        alive = _guide_walk_all(tab, s, tb, tl) != GUIDE_DEAD
+        alive = _guide_walk_all(tab, s, tb, tl, bound) != GUIDE_DEAD
         if 0 <= eos < alive.shape[0]:
             alive[eos] = False
         guide_flags[entry, s] = (int(guide_flags[entry, s]) & 1) | (0 if alive.any() else 2)
 
 
 def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, vocab_offset=0,
-               eos: int = -1, json_tab=None, json_state=None):
+               eos: int = -1, json_tab=None, json_state=None, tab_wide=None, flags_wide=None):
     """In place on logits [B, V] (row b = slot row_slot[b], else b).  Inactive rows, slots with the guide off and
     slots in the dead state are not touched.  Otherwise column v (global id g = v + vocab_offset) becomes -inf unless
     g is allowed: EOS iff the state is accepting or stuck, another token iff its bytes walk from the state without
     meeting dead; at a stuck state EOS becomes 0.0.  Allowed columns keep their bits.  A JSON-mode slot (entry
     JSON_ENTRY; json_state given) walks the pushdown automaton from its (state, depth, stack) instead; EOS is 0.0 iff
-    no other token of the global vocabulary survives (always so at JSON_DONE), else -inf."""
+    no other token of the global vocabulary survives (always so at JSON_DONE), else -inf.  A slot whose entry word is
+    GUIDE_POOL + e uses wide entry e (tab_wide / flags_wide given) with states below GUIDE_WIDE_STATES."""
     B, V = logits.shape
     slots = guide_meta.numel() // 2
     tb, tl = _guide_np(tok_bytes), _guide_np(tok_len)
@@ -585,13 +603,15 @@ def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
             if 0 <= js[0] < json_table()[0].shape[0] and 0 <= js[1] <= JSON_DEPTH:
                 _json_mask_row(logits[b], js, tb, tl, vocab_offset, eos)
             continue
-        if not 0 <= entry < guide_tab.shape[0] or not 0 <= state < GUIDE_STATES:
+        cls = _guide_class(guide_tab, guide_flags, entry, tab_wide, flags_wide)
+        if cls is None or not 0 <= state < cls[3]:
             continue
-        flags = int(guide_flags[entry, state])
+        tabs, flgs, entry, bound = cls
+        flags = int(flgs[entry, state])
         ok = np.zeros(V, dtype=bool)
         n = max(0, min(V, Vg - vocab_offset))
-        ok[:n] = _guide_walk_all(_guide_tab_np(guide_tab, entry), state, tb[vocab_offset:vocab_offset + n],
-                                 tl[vocab_offset:vocab_offset + n]) != GUIDE_DEAD
+        ok[:n] = _guide_walk_all(_guide_tab_np(tabs, entry), state, tb[vocab_offset:vocab_offset + n],
+                                 tl[vocab_offset:vocab_offset + n], bound) != GUIDE_DEAD
         e = eos - vocab_offset
         if 0 <= e < n:
             ok[e] = bool(flags & 3)
@@ -601,7 +621,7 @@ def guide_mask(logits, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
 
 
 def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide_meta, row_slot=None, eos: int = -1,
-                  json_tab=None, json_state=None):
+                  json_tab=None, json_state=None, tab_wide=None, flags_wide=None):
     """guide_meta's state of row b's slot = walk(state, bytes(ids[b])); EOS leaves it, a dead walk or a token of
     length 0 makes it GUIDE_DEAD.  Inactive rows and slots with the guide off are skipped.  A JSON-mode slot moves
     its json_state words instead (a dead walk writes the state word only)."""
@@ -618,10 +638,11 @@ def guide_advance(ids, active, tok_bytes, tok_len, guide_tab, guide_flags, guide
             else:
                 json_state.view(4, -1)[:, slot] = torch.tensor(json_state_words(js), dtype=torch.int32)
             continue
-        if not 0 <= entry < guide_tab.shape[0] or int(ids[b]) == eos:
+        cls = _guide_class(guide_tab, guide_flags, entry, tab_wide, flags_wide)
+        if cls is None or int(ids[b]) == eos:
             continue
-        guide_meta[slots + slot] = guide_walk(_guide_tab_np(guide_tab, entry), int(guide_meta[slots + slot]),
-                                              [int(ids[b])], tok_bytes, tok_len, eos)
+        guide_meta[slots + slot] = guide_walk(_guide_tab_np(cls[0], cls[2]), int(guide_meta[slots + slot]),
+                                              [int(ids[b])], tok_bytes, tok_len, eos, cls[3])
 
 
 # ---- JSON mode (response_format json_object): the pushdown walk of the language J (docs/kernels.md, "Sampler") ----

@@ -169,6 +169,7 @@ class EngineLoop(threading.Thread):
             min_p=float(req.get("min_p", 0.0)), stop=tuple(req.get("stop") or ()),
             # guided_regex, or guided_choice lowered to a pattern (compiled once by the HTTP server to validate it)
             guide=req.get("guide") or None,
+            guide_schema=bool(req.get("guide_schema")),  # guided_json / response_format json_schema, lowered
             json_object=bool(req.get("guide_json")))  # response_format {"type": "json_object"}
 
     def _watch_stop(self, req, prompt, params: SamplingParams) -> None:

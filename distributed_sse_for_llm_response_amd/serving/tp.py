@@ -68,7 +68,8 @@ class Plan:
                     raise ValueError(f"TP plan: seed {sd} outside [0, 2^62)")
                 s_lo, s_hi = sd & 0x7FFFFFFF, (sd >> 31) & 0x7FFFFFFF
             w += [rid, arrival & 0x7FFFFFFF, (arrival >> 31) & 0x7FFFFFFF, int(p.max_tokens), int(p.top_k), s_lo, s_hi,
-                  int(bool(p.ignore_eos)) | (2 if p.json_object else 0),  # (bit 1: JSON mode)
+                  # (bit 1: JSON mode; bit 2: the guide is schema-derived)
+                  int(bool(p.ignore_eos)) | (2 if p.json_object else 0) | (4 if p.guide_schema else 0),
                   _f2i(p.temperature), _f2i(p.top_p), _f2i(p.presence_penalty), _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), int(p.logprobs), int(p.min_tokens),
                   _f2i(p.min_p), len(p.logit_bias or ()), len(p.stop_token_ids), len(prompt)]
             guide = None if p.guide is None else p.guide.encode("utf-8")
@@ -111,7 +112,8 @@ class Plan:
                                 seed=None if s_lo < 0 else s_lo | (s_hi << 31), ignore_eos=bool(ie & 1),
                                 presence_penalty=_i2f(pres), frequency_penalty=_i2f(freq),
                                 repetition_penalty=_i2f(rep), logprobs=lp, logit_bias=bias or None, min_tokens=mn,
-                                stop_token_ids=stop_ids, min_p=_i2f(min_p), guide=guide, json_object=bool(ie & 2))
+                                stop_token_ids=stop_ids, min_p=_i2f(min_p), guide=guide, json_object=bool(ie & 2),
+                                guide_schema=bool(ie & 4))
             p.adds.append((rid, prompt, sp, a_lo | (a_hi << 31)))
         for _ in range(n_abort):
             p.aborts.append(w[o])

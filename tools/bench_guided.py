@@ -13,6 +13,10 @@
    start state, inside a string (the most permissive state) and at depth 64, over the synthetic vocabulary with 64 of
    its pieces replaced by JSON punctuation and fragments (the synthetic tokenizer has no braces); and the decode step
    with every stream in JSON mode on the runner's own (brace-less) table: inside a string, and stuck at the start state.
+With --wide, instead of all that and without a model: the mask pass, the advance pass and the one-off live pass for a
+4096-state table in the wide pool of schema guides (2 MiB, ops.guide_attach_wide) beside the same passes for the
+512-state narrow pattern, at `--streams` rows x V = 32768, rows spread over the table's states (the numbers of
+profiles/guided_json.md).
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -27,6 +31,9 @@ sys.path.insert(0, ROOT)
 
 PATTERN = "[a-z ]{255}[a-z ]{255}[a-z ]"  # 512 states; every lower-case word of the vocabulary survives
 DIGITS = "[0-9]{255}[0-9]{255}[0-9]"      # 512 states; all but ten tokens die at their first byte
+# about 4050 states under the wide caps: 16 chains of 253 that do not merge (each ends in its own letter); inside a
+# chain every lower-case word survives, as with PATTERN
+WIDE_PATTERN = "|".join(c + "[a-z ]{251}" + c for c in "abcdefghijkmnprs")
 JSON_PIECES = ["{", "}", "[", "]", '"', ":", ",", "\n", " ", "-", ".", "e", "E", "+", "true", "false", "null", '{"', '":',
                '",', '"}', "}}", "]}", "[[", '":"', '": "', '", "', "},{", "{}", "[]", "\\n", '\\"', "\\u00e9", "é",
                '":[', '":{', "}]", "]]", "],", "},", '"]', '"],', '":true', '":null', "\n  ", "\n    ", "1.5", "1e3", "-1",
@@ -40,6 +47,7 @@ def main():
     ap.add_argument("--streams", type=int, default=64)
     ap.add_argument("--ctx", type=int, default=512)
     ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--wide", action="store_true", help="time the guide passes for a 4096-state wide entry only")
     a = ap.parse_args()
 
     import numpy as np
@@ -72,6 +80,46 @@ def main():
 
     cfg = get_config(a.model)
     tok = SyntheticTokenizer(cfg.vocab_size)
+    if a.wide:
+        B, V = a.streams, cfg.vocab_size
+        tb, tl = (t.to(dev) for t in ops.guide_token_table(tok.pieces(), never={0, tok.eos_id}))
+        n, tab, acc = runtime.load().guide_compile_wide(WIDE_PATTERN)
+        wide = (np.frombuffer(tab, dtype=np.uint16).reshape(n, 256), np.frombuffer(acc, dtype=np.uint8))
+        gt = torch.full((1, ops.GUIDE_STATES, 256), -1, device=dev, dtype=torch.int16)
+        gf = torch.zeros(1, ops.GUIDE_STATES, device=dev, dtype=torch.int32)
+        wt = torch.full((1, ops.GUIDE_WIDE_STATES, 256), -1, device=dev, dtype=torch.int16)
+        wf = torch.zeros(1, ops.GUIDE_WIDE_STATES, device=dev, dtype=torch.int32)
+        meta = ops.guide_attach_wide(torch.zeros(2 * B, device=dev, dtype=torch.int32), wt, wf)
+        res = {"what": "guide passes, narrow 512-state entry against wide 4096-state entry", "rows": B, "V": V}
+        x = (torch.randn(B, V, device=dev) * 4).clamp_(-32, 32)
+        ids = torch.full((B,), tok.encode("ba", add_bos=False)[0], device=dev, dtype=torch.int32)
+        for name, (t, f), tabs, flgs, entry in (("narrow", compiled(PATTERN), gt, gf, 0),
+                                                ("wide", wide, wt, wf, ops.GUIDE_POOL)):
+            k = t.shape[0]
+            tabs[0, :k] = torch.from_numpy(t.view(np.int16).copy()).to(dev)
+            flgs[0, :k] = torch.from_numpy(f.astype(np.int32)).to(dev)
+            res[f"{name}_states"] = k
+            res[f"{name}_live_pass_us"] = timed_us(
+                lambda: ops.guide_live(tb, tl, gt, gf, meta, entry, k, tok.eos_id), n=10, warm=2)
+            m = torch.zeros(2 * B, dtype=torch.int32)
+            m[:B] = entry
+            for spread, states in (("start", torch.zeros(B)), ("spread", 1 + torch.arange(B) * ((k - 16) // B))):
+                m[B:] = states.to(torch.int32)
+                dm = m.to(dev)
+
+                def mask():
+                    meta.copy_(dm)
+                    ops.guide_mask(x.copy_(x.clamp(min=-32)), None, tb, tl, gt, gf, meta, None, 0, tok.eos_id)
+
+                def advance():
+                    meta.copy_(dm)
+                    ops.guide_advance(ids, None, tb, tl, gt, gf, meta, None, tok.eos_id)
+
+                res[f"{name}_mask_{spread}_us"] = timed_us(mask)
+                res[f"{name}_advance_{spread}_us"] = timed_us(advance)
+        res["row_restore_and_meta_upload_alone_us"] = timed_us(lambda: (meta.copy_(dm), x.copy_(x.clamp(min=-32))))
+        print(json.dumps(res), flush=True)
+        return
     w = random_engine_weights(cfg, device=dev, seed=0)
     B = a.streams
     pages = a.ctx // 32 + 2
