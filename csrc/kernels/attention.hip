@@ -56,7 +56,23 @@ DEV int part_keys(const AttnParams& p, int kmax) {
 // loaded in the matching head-dim order -- Q and K only have to agree inside the k-step set.
 template <int QW, int KWV, int PD = 1, int FQG = 0, typename KV = bf16>
 __global__ void __launch_bounds__(64 * QW * KWV, QW * KWV == 1 ? (PD > 1 ? 2 : 4) : 1)
-paged_attention_kernel(AttnParams p) {
+paged_attention_kernel(const int* __restrict__ work_seq, const int* __restrict__ work_tile,
+                       const int* __restrict__ q_len, const int* __restrict__ ctx_len,
+                       const int* __restrict__ q_start, const int* __restrict__ block_tables, int max_blocks,
+                       int nparts, AttnParams p_rest) {
+  // Argument order (docs/kernels.md "Kernel entry"): the entry is a chain of dependent scalar loads (work item ->
+  // sequence -> its lengths and query row -> block table -> first K page).  The 14 leading dwords, preloaded in
+  // SGPRs, are the pointers of that chain, so its first link is issued at once and the rest of AttnParams arrives
+  // from the kernarg segment under it.  `p` below is the full struct again (the leading copies are the same values).
+  AttnParams p = p_rest;
+  p.work_seq = work_seq;
+  p.work_tile = work_tile;
+  p.q_len = q_len;
+  p.ctx_len = ctx_len;
+  p.q_start = q_start;
+  p.block_tables = block_tables;
+  p.max_blocks = max_blocks;
+  p.nparts = nparts;
   constexpr bool FQ = FQG > 0;  // QKV epilogue folded in, GQA group FQG (= p.group)
   constexpr bool F8 = sizeof(KV) == 1;
   // head dim of element 0 of lane group g's fragment in k-step s (8 consecutive dims)
@@ -82,7 +98,7 @@ paged_attention_kernel(AttnParams p) {
   const int b = p.work_seq[item];
   const int qlen = p.q_len[b];
   const int ctx = p.ctx_len[b];
-  const int G = p.group, QT = 16 / G;
+  const int G = FQ ? FQG : p.group, QT = 16 / G;  // folded: a constant (the launcher picks FQG by p.group), no division
   const int tile = p.work_tile[item] * QW + qw;  // this wave's query tile
   const int q0 = tile * QT;                       // first query index (within the sequence)
 
@@ -551,14 +567,18 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(AttnParams p) {
   *reinterpret_cast<bf16x8*>(op) = ov;
 }
 
+// the kernel's leading (preloaded) arguments, then the whole struct
+#define DSSE_ATTN_ARGS(P) \
+  (P).work_seq, (P).work_tile, (P).q_len, (P).ctx_len, (P).q_start, (P).block_tables, (P).max_blocks, (P).nparts, (P)
+
 template <int G, typename KV>
 hipError_t launch_folded(int kwv, int pd, dim3 grid, const AttnParams& p, hipStream_t st) {
-  if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, G, KV>), grid, dim3(512), 0, st, p);
-  else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, G, KV>), grid, dim3(64), 0, st, p);
-  else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, G, KV>), grid, dim3(64), 0, st, p);
-  else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, G, KV>), grid, dim3(128), 0, st, p);
-  else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, G, KV>), grid, dim3(128), 0, st, p);
-  else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, G, KV>), grid, dim3(256), 0, st, p);
+  if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, G, KV>), grid, dim3(512), 0, st, DSSE_ATTN_ARGS(p));
+  else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, G, KV>), grid, dim3(64), 0, st, DSSE_ATTN_ARGS(p));
+  else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, G, KV>), grid, dim3(64), 0, st, DSSE_ATTN_ARGS(p));
+  else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, G, KV>), grid, dim3(128), 0, st, DSSE_ATTN_ARGS(p));
+  else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, G, KV>), grid, dim3(128), 0, st, DSSE_ATTN_ARGS(p));
+  else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, G, KV>), grid, dim3(256), 0, st, DSSE_ATTN_ARGS(p));
   return hipGetLastError();
 }
 
@@ -596,17 +616,17 @@ hipError_t launch_paged(int mode, int num_work, const AttnParams* p, hipStream_t
     const dim3 grid(num_work, p->hkv, p->nparts);
     const int kwv = p->kwv ? p->kwv : (grid.x * grid.y * grid.z >= 2048 ? 1 : 4);
     const int pd = p->pd == 2 && kwv <= 2 ? 2 : 1;  // attn_pd=2 (DSSE_KERNEL_CFG): 2-page register ring (1 / 2 waves)
-    if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, 0, KV>), grid, dim3(512), 0, st, *p);
-    else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, 0, KV>), grid, dim3(64), 0, st, *p);
-    else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, 0, KV>), grid, dim3(128), 0, st, *p);
-    else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, 0, KV>), grid, dim3(64), 0, st, *p);
-    else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, 0, KV>), grid, dim3(128), 0, st, *p);
-    else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, 0, KV>), grid, dim3(256), 0, st, *p);
+    if (kwv == 8) hipLaunchKernelGGL((paged_attention_kernel<1, 8, 1, 0, KV>), grid, dim3(512), 0, st, DSSE_ATTN_ARGS(*p));
+    else if (kwv == 1 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 2, 0, KV>), grid, dim3(64), 0, st, DSSE_ATTN_ARGS(*p));
+    else if (kwv == 2 && pd == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 2, 0, KV>), grid, dim3(128), 0, st, DSSE_ATTN_ARGS(*p));
+    else if (kwv == 1) hipLaunchKernelGGL((paged_attention_kernel<1, 1, 1, 0, KV>), grid, dim3(64), 0, st, DSSE_ATTN_ARGS(*p));
+    else if (kwv == 2) hipLaunchKernelGGL((paged_attention_kernel<1, 2, 1, 0, KV>), grid, dim3(128), 0, st, DSSE_ATTN_ARGS(*p));
+    else hipLaunchKernelGGL((paged_attention_kernel<1, 4, 1, 0, KV>), grid, dim3(256), 0, st, DSSE_ATTN_ARGS(*p));
     if (p->nparts > 1 && !p->comb_cnt)
       hipLaunchKernelGGL((attn_combine_kernel<1, F8>), dim3(num_work, p->hkv, 1), dim3(256), 0, st, *p);
   } else {
     hipLaunchKernelGGL((paged_attention_kernel<4, 1, 1, 0, KV>), dim3(num_work, p->hkv, p->nparts), dim3(256),
-                       0, st, *p);
+                       0, st, DSSE_ATTN_ARGS(*p));
     if (p->nparts > 1)
       hipLaunchKernelGGL((attn_combine_kernel<4, F8>), dim3(num_work, p->hkv, 4), dim3(256), 0, st, *p);
   }

@@ -19,16 +19,17 @@ DEV int vperm_tok(int off) { return ((off & 15) >> 2) * 8 + ((off >> 4) & 1) * 4
 // as many waves as possible to keep enough loads in flight); each thread owns H / (4·threads) float4s.
 template <int MODE>
 __global__ void __launch_bounds__(1024)
-rmsnorm_kernel(float* __restrict__ resid, int H, const bf16* __restrict__ delta,
-               const bf16* __restrict__ embed, const int* __restrict__ ids,
-               const bf16* __restrict__ w, bf16* __restrict__ y, float eps,
-               const float* __restrict__ part = nullptr, int nsplit = 0, int M = 0, int vocab = 0) {
-  const int m = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+rmsnorm_kernel(float* __restrict__ resid, const float* __restrict__ part, const bf16* __restrict__ w,
+               const int* __restrict__ ids, const bf16* __restrict__ embed, int nt, int nit, int nsplit, int M,
+               const bf16* __restrict__ delta, bf16* __restrict__ y, float eps, int vocab) {
+  // Argument order (docs/kernels.md "Kernel entry"): the 14 dwords up to M arrive preloaded in SGPRs and address every
+  // load of the row.  nt = the block size (blockDim is a hidden kernel argument: a round trip before the first load)
+  // and nit = float4s per thread, both from the host: H = 4 nt nit exactly, so no division on the way to the loads.
+  const int m = blockIdx.x, tid = threadIdx.x, H = 4 * nt * nit;
   const unsigned long long st0 = stamps::now();
   float* rrow = resid + (size_t)m * H;
   constexpr int kMaxIt = 2;  // H <= 8192
   float4 v[kMaxIt];
-  const int nit = H / (4 * nt);
   float ss = 0.f;
   // the norm weights are loaded with the row, not after the block reduction: one dependent round trip fewer
   bf16x4 wv[kMaxIt];
@@ -306,11 +307,12 @@ silu_mul_kernel(const bf16* __restrict__ gu, bf16* __restrict__ h, int F, int T)
 
 // ---- decode-step metadata (runs first inside the captured graph) -----------------------------
 // For slot b: live sequences process the token at positions[b]; dead slots write nothing.
-__global__ void decode_prep_kernel(int B, const int* __restrict__ active, const int* __restrict__ positions,
+constexpr int kPrepThreads = 256;
+__global__ void __launch_bounds__(kPrepThreads) decode_prep_kernel(int B, const int* __restrict__ active, const int* __restrict__ positions,
                                    const int* __restrict__ block_tables, int max_blocks, int num_blocks,
                                    int* __restrict__ slots, int* __restrict__ ctx_len,
                                    int* __restrict__ q_len) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.x * kPrepThreads + threadIdx.x;  // (blockDim is a hidden kernel argument)
   if (b >= B) return;
   if (active[b]) {
     const int pos = positions[b];
@@ -345,10 +347,10 @@ extern "C" hipError_t dsse_rmsnorm(int mode, int M, float* resid, int H, const v
   const int nit = (H / 4 + 1023) / 1024, nt = H / 4 / nit;
   if (nit > 2 || 4 * nt * nit != H || nt % 64 != 0) return hipErrorInvalidValue;
   switch (mode) {
-    case 0: hipLaunchKernelGGL(rmsnorm_kernel<0>, dim3(M), dim3(nt), 0, st, resid, H, d, e, ids, wp, yp, eps, part, nsplit, M, vocab); break;
-    case 1: hipLaunchKernelGGL(rmsnorm_kernel<1>, dim3(M), dim3(nt), 0, st, resid, H, d, e, ids, wp, yp, eps, part, nsplit, M, vocab); break;
-    case 2: hipLaunchKernelGGL(rmsnorm_kernel<2>, dim3(M), dim3(nt), 0, st, resid, H, d, e, ids, wp, yp, eps, part, nsplit, M, vocab); break;
-    case 3: hipLaunchKernelGGL(rmsnorm_kernel<3>, dim3(M), dim3(nt), 0, st, resid, H, d, e, ids, wp, yp, eps, part, nsplit, M, vocab); break;
+    case 0: hipLaunchKernelGGL(rmsnorm_kernel<0>, dim3(M), dim3(nt), 0, st, resid, part, wp, ids, e, nt, nit, nsplit, M, d, yp, eps, vocab); break;
+    case 1: hipLaunchKernelGGL(rmsnorm_kernel<1>, dim3(M), dim3(nt), 0, st, resid, part, wp, ids, e, nt, nit, nsplit, M, d, yp, eps, vocab); break;
+    case 2: hipLaunchKernelGGL(rmsnorm_kernel<2>, dim3(M), dim3(nt), 0, st, resid, part, wp, ids, e, nt, nit, nsplit, M, d, yp, eps, vocab); break;
+    case 3: hipLaunchKernelGGL(rmsnorm_kernel<3>, dim3(M), dim3(nt), 0, st, resid, part, wp, ids, e, nt, nit, nsplit, M, d, yp, eps, vocab); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -402,7 +404,7 @@ extern "C" hipError_t dsse_silu_mul(int T, int F, const void* gu, void* h, hipSt
 extern "C" hipError_t dsse_decode_prep(int B, const int* active, const int* positions,
                                        const int* block_tables, int max_blocks, int num_blocks, int* slots,
                                        int* ctx_len, int* q_len, hipStream_t st) {
-  hipLaunchKernelGGL(decode_prep_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, active,
+  hipLaunchKernelGGL(decode_prep_kernel, dim3((B + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, st, B, active,
                      positions, block_tables, max_blocks, num_blocks, slots, ctx_len, q_len);
   return hipGetLastError();
 }

@@ -309,6 +309,23 @@ struct RingGeom {
   static constexpr size_t LDS = (size_t)D * SLOT;
 };
 
+// XCD-grouped split-K numbering of the ring kernels, decided on the host (it depends on the launch only): dispatch
+// deals workgroup i, x-fastest, to XCD i % 8; with S in {2, 4, 8} slices and gx * S a multiple of 8, each K range
+// stays on per = 8 / S XCDs, so an XCD's L2 fetches only its K range of X.  xs = log2(per), or -1 for the plain
+// (blockIdx.x, blockIdx.y) numbering.  Bijective, speed only.  The kernels take gx and xs as leading arguments: a
+// wave must not wait for gridDim (a hidden kernel argument) or divide on its way to the first load.
+static inline int xcd_split_shift(int gx, int S) {
+  if (!DSSE_XCD_SPLITK || S <= 1 || 8 % S != 0 || (gx * S) % 8 != 0) return -1;
+  return S == 2 ? 2 : (S == 4 ? 1 : 0);
+}
+DEV void xcd_split(int gx, int xs, int& wg, int& ks) {
+  if (xs >= 0) {
+    const int lin = blockIdx.y * gx + blockIdx.x, xcd = lin & 7, slot = lin >> 3;
+    ks = xcd >> xs;
+    wg = (slot << xs) + (xcd & ((1 << xs) - 1));
+  }
+}
+
 DEV void glds16_s(const void* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds(const_cast<void*>(src),
                                    reinterpret_cast<__attribute__((address_space(3))) void*>(
@@ -324,7 +341,9 @@ DEV void glds16_s(const void* src, char* lds_base) {
 template <int MT, int NW, int D, int MODE, bool FIX = false>
 __global__ void __launch_bounds__(64 * NW)
 gemm_ring_kernel(const bf16* __restrict__ X, int ldx, int M, const bf16* __restrict__ W, int K, int N, int Kr,
-                 GemmEpi ep, float* __restrict__ part) {
+                 int gx, int xs, int S, float* __restrict__ part, GemmEpi ep) {
+  // Argument order (docs/kernels.md "Kernel entry"): the 14 dwords up to `part` arrive preloaded in SGPRs and are
+  // all the first DMA burst needs; `ep` is read by the epilogue only.  gx = gridDim.x, S = gridDim.y, xs: xcd_split.
   using G = RingGeom<MT, NW, D>;
   constexpr int MP = 16 * MT;
   constexpr int XN = MP / 4;               // 1 KiB X DMA instructions per chunk (4 rows each)
@@ -340,11 +359,7 @@ gemm_ring_kernel(const bf16* __restrict__ X, int ldx, int M, const bf16* __restr
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   int wg = blockIdx.x, ks = blockIdx.y;
-  if (DSSE_XCD_SPLITK && gridDim.y > 1 && 8 % gridDim.y == 0 && (gridDim.x * gridDim.y) % 8 == 0) {
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x, xcd = lin % 8, slot = lin / 8, per = 8 / gridDim.y;
-    ks = xcd / per;
-    wg = slot * per + xcd % per;
-  }
+  xcd_split(gx, xs, wg, ks);
   const int tgi = wg * NW + w;  // this wave's 16-column tile
   const int k0 = ks * Kr;
   const int nch = Kr >> 7;
@@ -412,7 +427,6 @@ gemm_ring_kernel(const bf16* __restrict__ X, int ldx, int M, const bf16* __restr
   const unsigned long long st2 = stamps::now();
 
   if constexpr (FIX) {
-    const int S = gridDim.y;
     if (S > 1) {
       typedef __attribute__((address_space(1))) int gint;  // shared words: global agent-scope accesses
       gint* cnt = (gint*)(ep.fix_cnt) + 4;                 // tickets [wg], done [kFixTiles + wg]; timeouts at [0]
@@ -493,8 +507,8 @@ static hipError_t launch_r(const bf16* X, int ldx, int M, const bf16* W, int K, 
     attr_set = true;
   }
   dim3 grid(N / 16 / NW, S), block(64 * NW);
-  hipLaunchKernelGGL((gemm_ring_kernel<MT, NW, D, MODE, FIX>), grid, block, lds, st, X, ldx, M, W, K, N, K / S, ep,
-                     part);
+  hipLaunchKernelGGL((gemm_ring_kernel<MT, NW, D, MODE, FIX>), grid, block, lds, st, X, ldx, M, W, K, N, K / S,
+                     (int)grid.x, xcd_split_shift((int)grid.x, S), S, part, ep);
   return hipGetLastError();
 }
 
@@ -562,7 +576,7 @@ struct Ring2Geom {
 template <int MT, int NW, int XL, int DX, int DW, int MODE>
 __global__ void __launch_bounds__(64 * (NW + XL))
 gemm_ring2_kernel(const bf16* __restrict__ X, int ldx, int M, const bf16* __restrict__ W, int K, int N, int Kr,
-                  GemmEpi ep, float* __restrict__ part) {
+                  int gx, int xs, int S, float* __restrict__ part, GemmEpi ep) {
   using G = Ring2Geom<MT, NW, XL, DX, DW>;
   constexpr int MP = 16 * MT;
   constexpr int XN = MP / 4;              // 1 KiB X DMA instructions per chunk (4 rows each)
@@ -575,11 +589,7 @@ gemm_ring2_kernel(const bf16* __restrict__ X, int ldx, int M, const bf16* __rest
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   int wg = blockIdx.x, ks = blockIdx.y;
-  if (DSSE_XCD_SPLITK && gridDim.y > 1 && 8 % gridDim.y == 0 && (gridDim.x * gridDim.y) % 8 == 0) {
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x, xcd = lin % 8, slot = lin / 8, per = 8 / gridDim.y;
-    ks = xcd / per;
-    wg = slot * per + xcd % per;
-  }
+  xcd_split(gx, xs, wg, ks);
   const int k0 = ks * Kr;
   const int nch = Kr >> 7;
   const int KC = K >> 7;
@@ -688,7 +698,7 @@ static hipError_t launch_r2(const bf16* X, int ldx, int M, const bf16* W, int K,
   }
   dim3 grid(N / 16 / NW, S), block(64 * (NW + XL));
   hipLaunchKernelGGL((gemm_ring2_kernel<MT, NW, XL, DX, DW, MODE>), grid, block, lds, st, X, ldx, M, W, K, N, K / S,
-                     ep, part);
+                     (int)grid.x, xcd_split_shift((int)grid.x, S), S, part, ep);
   return hipGetLastError();
 }
 

@@ -59,7 +59,28 @@ DEV void block_argmax(float& best, int& bidx, float* s_best, int* s_bidx) {
 
 // Unfiltered rows (greedy or pure temperature): Gumbel-max is separable, so each (row, chunk)
 // workgroup proposes the best (score, index) of its vocab slice.
-__global__ void __launch_bounds__(kCThreads) sample_chunk_kernel(SampleParams p) {
+// Both candidate kernels open by reading the row's switches (active, temperature, top-k / top-p / min_p): those
+// pointers and the logits row's address lead the argument list (14 dwords, preloaded in SGPRs), so the first loads
+// do not wait for a trip to the kernarg segment; the rest of SampleParams arrives under them.
+#define DSSE_SAMPLE_LEAD const int *__restrict__ active, const float *__restrict__ temperature,                     \
+                         const int *__restrict__ top_k, const float *__restrict__ top_p,                          \
+                         const float *__restrict__ logits, const float *__restrict__ min_p, int ld, int V
+#define DSSE_SAMPLE_ARGS(P) (P).active, (P).temperature, (P).top_k, (P).top_p, (P).logits, (P).min_p, (P).ld, (P).V, (P)
+DEV SampleParams sample_params(DSSE_SAMPLE_LEAD, const SampleParams& rest) {
+  SampleParams p = rest;  // the leading arguments are the same values
+  p.active = active;
+  p.temperature = temperature;
+  p.top_k = top_k;
+  p.top_p = top_p;
+  p.logits = logits;
+  p.min_p = min_p;
+  p.ld = ld;
+  p.V = V;
+  return p;
+}
+
+__global__ void __launch_bounds__(kCThreads) sample_chunk_kernel(DSSE_SAMPLE_LEAD, SampleParams p_rest) {
+  const SampleParams p = sample_params(active, temperature, top_k, top_p, logits, min_p, ld, V, p_rest);
   const int c = blockIdx.x, b = blockIdx.y;
   if ((p.active && !p.active[b]) || row_filtered(p, b)) return;
   __shared__ float s_best[kCThreads / 64];
@@ -131,7 +152,8 @@ DEV float block_max(float v, float* sh) {
 }
 
 // Rows with top-k / top-p: one workgroup per row, the whole (local) row staged in LDS.
-__global__ void __launch_bounds__(kSThreads) sample_filtered_kernel(SampleParams p) {
+__global__ void __launch_bounds__(kSThreads) sample_filtered_kernel(DSSE_SAMPLE_LEAD, SampleParams p_rest) {
+  const SampleParams p = sample_params(active, temperature, top_k, top_p, logits, min_p, ld, V, p_rest);
   const int b = blockIdx.x;
   if ((p.active && !p.active[b]) || !row_filtered(p, b)) return;
   __shared__ float xs[kSMaxV];
@@ -516,8 +538,15 @@ __global__ void sample_hist_append_kernel(const int* __restrict__ new_ids, int n
 
 // Merge candidates [world, B, nchunks] (vocab chunks x tensor-parallel shards) and commit the token:
 // next_ids[b], ring[head][b], positions[b] += 1 (and, with p.hist, the history append of slot b).
-__global__ void sample_pick_kernel(const float2* __restrict__ cand, int world, int B, SampleParams p) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+constexpr int kPickThreads = 64;
+__global__ void __launch_bounds__(kPickThreads)
+sample_pick_kernel(const float2* __restrict__ cand, int world, int B, int nchunks, const int* __restrict__ active,
+                   SampleParams p_rest) {
+  // cand, the loop bounds and `active` lead (preloaded); the block size is a constant (blockDim is a hidden argument)
+  SampleParams p = p_rest;
+  p.nchunks = nchunks;
+  p.active = active;
+  const int b = blockIdx.x * kPickThreads + threadIdx.x;
   if (b >= B) return;
   if (p.active && !p.active[b]) return;
   float best = -INFINITY;
@@ -857,8 +886,9 @@ extern "C" hipError_t dsse_sample_hist_append(int n, const int* new_ids, const d
 extern "C" hipError_t dsse_sample(int B, const dsse::SampleParams* p, hipStream_t st) {
   if (B <= 0) return hipSuccess;
   if (p->V > dsse::kSMaxV || p->nchunks < 1 || (p->min_p && p->ctl_slots < 1)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(dsse::sample_chunk_kernel, dim3(p->nchunks, B), dim3(dsse::kCThreads), 0, st, *p);
-  hipLaunchKernelGGL(dsse::sample_filtered_kernel, dim3(B), dim3(dsse::kSThreads), 0, st, *p);
+  hipLaunchKernelGGL(dsse::sample_chunk_kernel, dim3(p->nchunks, B), dim3(dsse::kCThreads), 0, st,
+                     DSSE_SAMPLE_ARGS(*p));
+  hipLaunchKernelGGL(dsse::sample_filtered_kernel, dim3(B), dim3(dsse::kSThreads), 0, st, DSSE_SAMPLE_ARGS(*p));
   return hipGetLastError();
 }
 
@@ -866,8 +896,9 @@ extern "C" hipError_t dsse_sample(int B, const dsse::SampleParams* p, hipStream_
 extern "C" hipError_t dsse_sample_pick(int B, int world, const void* cand, const dsse::SampleParams* p,
                                        hipStream_t st) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL(dsse::sample_pick_kernel, dim3((B + 63) / 64), dim3(64), 0, st,
-                     reinterpret_cast<const float2*>(cand), world, B, *p);
+  hipLaunchKernelGGL(dsse::sample_pick_kernel, dim3((B + dsse::kPickThreads - 1) / dsse::kPickThreads),
+                     dim3(dsse::kPickThreads), 0, st, reinterpret_cast<const float2*>(cand), world, B, p->nchunks,
+                     p->active, *p);
   return hipGetLastError();
 }
 

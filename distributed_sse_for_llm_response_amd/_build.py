@@ -72,7 +72,22 @@ KERNEL_VARIANTS = {
     "checked": ["-DDSSE_KERNEL_CHECKS=1"],  # device index-check debug build (tools/check_kernels.py)
     "burst": ["-DDSSE_TILED_BURST=1"],  # A/B build: gemm_tiled issues each stage's DMA in one burst
     "stamps": ["-DDSSE_PIPE_STAMPS=1"],  # diagnostic build: gemm_pipe FIX phase stamps (tools/pipe_stamps.py)
+    "nopreload": [],  # A/B build: kernel arguments fetched from the kernarg segment (no SGPR preload)
+    "stamps_nopreload": ["-DDSSE_PIPE_STAMPS=1"],  # the stamps build without the preload (tools/step_stamps.py A/B)
 }  # libdsse_kernels_<variant>.so, selected at import with DSSE_KERNELS_VARIANT
+
+# Kernarg preloading (docs/kernels.md "Kernel entry"): the leading kernel arguments arrive in user SGPRs at wave
+# launch instead of through an s_load round trip to the kernarg segment.  16 is the hardware's user-SGPR total;
+# the compiler preloads as many leading arguments as fit after the ones it reserves.
+KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+
+
+def kernel_device_flags(variant: str | None = None) -> list[str]:
+    """Flags of the device side of a csrc/kernels/*.hip compile (tests/test_kernel_entry_cpu.py builds with them)."""
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", *KERNEL_VARIANTS.get(variant, []), "-munsafe-fp-atomics"]
+    if not (variant or "").endswith("nopreload"):
+        flags += KERNARG_PRELOAD
+    return flags
 
 
 def kernels_so(variant: str | None = None) -> Path:
@@ -95,7 +110,8 @@ def build_kernels(verbose: bool = False, force: bool = False, variant: str | Non
         obj = obj_dir / (src.stem + ".o")
         objs.append(obj)
         if force or _stale(obj, [src, *headers]):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", *common, "-munsafe-fp-atomics", "-c", src, "-o", obj])
+            jobs.append([HIPCC, *kernel_device_flags(variant), "-fPIC", f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
+                         "-Wno-unused-result", "-c", src, "-o", obj])
     bsrc = kdir / "bindings.cpp"
     bobj = obj_dir / "bindings.o"
     objs.append(bobj)
