@@ -282,6 +282,10 @@ hipError_t dsse_ring_advance(int* counter, hipStream_t st);
 // the records back into the listed pages.  seg_bytes = Hkv * 4096 * itemsize (a multiple of 16); n = 0 launches nothing.
 hipError_t dsse_kv_pages(int gather, int n, void* k_cache, void* v_cache, const int* blocks, void* staging, int L,
                          int num_blocks, unsigned seg_bytes, hipStream_t st);
+// Page-to-page copy inside the cache (parallel sampling): pairs = [n, 2] (src_block, dst_block) in device memory; all
+// 2 L segments of page src are copied onto page dst.  Destinations are distinct and none is a source (the host checks).
+hipError_t dsse_kv_pages_copy(int n, void* k_cache, void* v_cache, const int* pairs, int L, int num_blocks,
+                              unsigned seg_bytes, hipStream_t st);
 // TP all-reduce + residual + RMSNorm over IPC peer buffers (allreduce.hip)
 size_t dsse_ar_buffer_bytes(int rows, int H);
 hipError_t dsse_ar_alloc(size_t bytes, void** ptr, void* handle64, int* uncached);

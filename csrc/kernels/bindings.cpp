@@ -1657,6 +1657,41 @@ void kv_pages_scatter(const Tensor& staging, const Tensor& blocks, Tensor& k_cac
   kv_pages(false, k_cache, v_cache, blocks, staging);
 }
 
+// Page-to-page copy inside the cache (kv_pages.hip kv_pages_copy_kernel): pairs = [n, 2] int32 (src, dst).  As above,
+// the VALUES are validated on the host by ops.kv_pages_copy (range, distinct destinations, no destination a source).
+void kv_pages_copy(Tensor& k_cache, Tensor& v_cache, const Tensor& pairs) {
+  check_gpu(k_cache, "k_cache");
+  check_gpu(v_cache, "v_cache");
+  check_gpu(pairs, "pairs");
+  check_dtype(pairs, at::kInt, "pairs");
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 || k_cache.scalar_type() == at::kFloat8_e4m3fn,
+              "k_cache has dtype ", k_cache.scalar_type(), ", expected bfloat16 or float8_e4m3fn");
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type(), "v_cache has dtype ", v_cache.scalar_type(),
+              ", but k_cache has ", k_cache.scalar_type());
+  TORCH_CHECK(k_cache.dim() == 5 && k_cache.size(3) == dsse::kBS && k_cache.size(4) == 128,
+              "k_cache must be [L, blocks, Hkv, 32, 128]");
+  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(3) == 128 && v_cache.size(4) == dsse::kBS &&
+                  v_cache.size(0) == k_cache.size(0) && v_cache.size(1) == k_cache.size(1) &&
+                  v_cache.size(2) == k_cache.size(2),
+              "v_cache must be [L, blocks, Hkv, 128, 32] with k_cache's L, blocks and Hkv");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous(), "kv_pages_copy: the caches must be contiguous");
+  TORCH_CHECK(k_cache.device() == v_cache.device() && k_cache.device() == pairs.device(),
+              "kv_pages_copy: every tensor must be on the same device");
+  const int64_t L = k_cache.size(0), nb = k_cache.size(1), hkv = k_cache.size(2);
+  const int64_t seg = hkv * dsse::kBS * 128 * (int64_t)k_cache.element_size();
+  TORCH_CHECK(L >= 1 && nb >= 1 && hkv >= 1 && nb <= INT_MAX && seg % 16 == 0 && seg <= UINT_MAX && 2 * L <= INT_MAX,
+              "kv_pages_copy: unsupported cache shape");
+  TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.is_contiguous(),
+              "pairs must be a contiguous [n, 2] int32 list of (src_block, dst_block)");
+  const int64_t n = pairs.size(0);
+  TORCH_CHECK(n <= 65535, "pairs lists ", n, " copies; one launch moves 65535 at most");
+  for (const Tensor* t : {&k_cache, &v_cache})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "kv_pages_copy: tensors must be 16-byte aligned");
+  if (n == 0) return;  // nothing is launched
+  DSSE_CHECK_HIP(dsse_kv_pages_copy((int)n, k_cache.data_ptr(), v_cache.data_ptr(), pairs.data_ptr<int>(), (int)L,
+                                    (int)nb, (unsigned)seg, cur_stream()));
+}
+
 int64_t kernels_abi_version() { return 16; }
 
 // The dispatch's choice for an (M, N, K) projection: (impl, tiled cfg, split, fix, model estimate in us) -- impl as
@@ -1774,6 +1809,7 @@ TORCH_LIBRARY(dsse, m) {
   m.def("ring_advance(Tensor(a!) counter) -> ()");
   m.def("kv_pages_gather(Tensor k_cache, Tensor v_cache, Tensor blocks, Tensor(a!) staging) -> ()");
   m.def("kv_pages_scatter(Tensor staging, Tensor blocks, Tensor(a!) k_cache, Tensor(b!) v_cache) -> ()");
+  m.def("kv_pages_copy(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor pairs) -> ()");
   m.def("paged_attention(int mode, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor q_start, Tensor q_len, Tensor ctx_len, Tensor work_seq, Tensor work_tile, Tensor(a!) out, "
         "Tensor(b!) part_o, Tensor(c!) part_ml, int part, int nparts, float k_scale=1.0, float v_scale=1.0) -> ()");
@@ -1851,6 +1887,7 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("ring_advance", &ring_advance);
   m.impl("kv_pages_gather", &kv_pages_gather);
   m.impl("kv_pages_scatter", &kv_pages_scatter);
+  m.impl("kv_pages_copy", &kv_pages_copy);
   m.impl("paged_attention", &paged_attention);
   m.impl("flash_prefill_split", &flash_prefill_split);
   m.impl("qkv_attention_decode", &qkv_attention_decode);

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <set>
 
 #include "metrics.h"
 #include "util.h"
@@ -49,6 +50,7 @@ std::string encode_request(const ChatRequest& r) {
   w.str(r.guide);
   w.u8(r.guide_json ? 1 : 0);
   w.u8(r.guide_schema ? 1 : 0);
+  w.i32(r.n);
   return w.data();
 }
 
@@ -87,6 +89,8 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   if (r->guide.size() > 8192) return false;
   r->guide_json = rd.u8() != 0;
   r->guide_schema = rd.u8() != 0;
+  r->n = rd.i32();
+  if (r->n < 1 || r->n > 16) return false;
   return rd.good();
 }
 }  // namespace dpwire
@@ -222,6 +226,17 @@ bool DpRouter::send_request_locked(ChatRequest r) {
   if (w < 0) return false;
   const std::string msg = dpwire::encode_request(r);
   if (!to_w_[(size_t)w]->push_wait(msg.data(), (uint32_t)msg.size(), 1000)) return false;
+  // parallel sampling: every choice of the request lives on this replica.  The sibling ids are tracked like
+  // conversations of their own (tokens, cancellations and flow control find their worker; each counts as outstanding
+  // until its own terminal frame), but carry no request: only choice 0 is ever re-sent.
+  for (int i = 1; i < r.n; ++i) {
+    auto& sc = convs_[choice_conversation_id(r.conversation_id, i)];
+    if (sc.worker != w) info_[(size_t)w].outstanding++;
+    sc.worker = w;
+    sc.last_seq = 0;
+    sc.req = ChatRequest{};
+    sc.root = r.conversation_id;
+  }
   auto& c = convs_[r.conversation_id];
   if (c.worker != w) info_[(size_t)w].outstanding++;
   c.worker = w;
@@ -247,12 +262,34 @@ void DpRouter::check_liveness_locked(int64_t now_ms) {
     log_json(LogLevel::kWarn, "dp worker lost", "\"worker\":" + std::to_string(w));
     std::vector<ChatRequest> requeue;
     std::vector<FramePtr> errors;
+    // What becomes of this worker's conversations.  A request with n > 1 is one unit, named by its choice 0 (`root`):
+    //   n = 1 / choice 0, no token delivered, no sibling has one  -> re-sent (`resend`; the siblings ride along)
+    //   sibling of a re-sent choice 0                              -> erased silently (re-registered by the re-send)
+    //   any choice of a request that has delivered a token         -> [ERROR] (every choice of it that is still here)
+    //   sibling whose choice 0 is gone (it finished earlier)       -> [ERROR]
+    std::set<std::string> started;
+    for (auto& kv : convs_)
+      if (kv.second.worker == w && kv.second.last_seq != 0)
+        started.insert(kv.second.root.empty() ? kv.first : kv.second.root);
+    std::set<std::string> resend;  // choice 0 ids that go back to the queue, with all their siblings
+    for (auto& kv : convs_)
+      if (kv.second.worker == w && kv.second.root.empty() && kv.second.last_seq == 0 && !started.count(kv.first))
+        resend.insert(kv.first);
     for (auto it = convs_.begin(); it != convs_.end();) {
       if (it->second.worker != w) {
         ++it;
         continue;
       }
-      if (it->second.last_seq == 0) {
+      const std::string& root = it->second.root.empty() ? it->first : it->second.root;
+      const bool fresh = it->second.last_seq == 0 && !started.count(root);
+      if (fresh && !it->second.root.empty()) {
+        // a sibling of a request that is re-sent (or whose choice 0 is gone): send_request_locked registers it again
+        if (resend.count(root)) {
+          it = convs_.erase(it);
+          continue;
+        }
+      }
+      if (fresh && it->second.root.empty()) {
         requeue.push_back(std::move(it->second.req));
       } else {
         TokenMessage m{it->first, "[ERROR]", it->second.last_seq + 1, true, now_ns()};
@@ -387,6 +424,11 @@ void DpRouter::drain_loop(int w) {
           if (rd.good()) metrics().observe_kv_offload(sp, rs, dr, ht);
         }
       }
+      const int32_t nf = rd.good() ? rd.i32() : 0;
+      if (nf == 3 && rd.good()) {
+        const double rq = rd.f64(), sh = rd.f64(), tc = rd.f64();
+        if (rd.good()) metrics().observe_parallel_sampling(rq, sh, tc);
+      }
       if (step_s > 0) metrics().engine_decode_step_seconds.observe(step_s);
       double batch = 0, kv = 0, active = 0;
       for (auto& x : info_) {
@@ -490,7 +532,7 @@ void DpWorker::bye() {
 
 void DpWorker::stats(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,
                      const std::vector<double>& itl, const std::vector<double>& host,
-                     const std::vector<double>& prefix) {
+                     const std::vector<double>& prefix, const std::vector<double>& fork) {
   dpwire::Writer m;
   m.u8(dpwire::kStats);
   m.f64(step_s);
@@ -506,6 +548,9 @@ void DpWorker::stats(double step_s, double batch, double kv_free, double active,
   // prefix caching on: [queries, hits, evictions] since the last message (empty: the feature is off)
   m.i32((int32_t)prefix.size());
   for (double v : prefix) m.f64(v);
+  // parallel sampling: [requests, shared tokens, tail copies] since the last message (empty: none seen so far)
+  m.i32((int32_t)fork.size());
+  for (double v : fork) m.f64(v);
   send(m.data());
 }
 

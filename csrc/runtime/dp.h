@@ -119,6 +119,7 @@ class DpRouter {
     int worker = -1;
     int64_t last_seq = 0;
     ChatRequest req;
+    std::string root;  // a sibling choice of a request with n > 1: its choice 0's id ("" for choice 0 / n = 1)
   };
   void dispatch_loop();
   void drain_loop(int w);
@@ -166,7 +167,7 @@ class DpWorker {
   void bye();
   void stats(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,
              const std::vector<double>& itl, const std::vector<double>& host = {},
-             const std::vector<double>& prefix = {});
+             const std::vector<double>& prefix = {}, const std::vector<double>& fork = {});
 
  private:
   void heartbeat_if_due();

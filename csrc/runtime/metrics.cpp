@@ -141,6 +141,15 @@ std::string Metrics::render() const {
     line(o, "engine_prefix_cache_evictions_total", "KV pages evicted from the prefix cache", "counter",
          engine_prefix_cache_evictions_total.get());
   }
+  if (parallel_sampling_on.load(std::memory_order_relaxed)) {
+    line(o, "engine_parallel_sampling_requests_total", "Requests with n > 1 (several choices of one prompt)", "counter",
+         engine_parallel_sampling_requests_total.get());
+    line(o, "engine_parallel_sampling_shared_tokens_total",
+         "Prompt tokens sibling choices took from the first choice's KV pages instead of prefilling them", "counter",
+         engine_parallel_sampling_shared_tokens_total.get());
+    line(o, "engine_parallel_sampling_tail_copies_total", "Partial last prompt pages copied for sibling choices",
+         "counter", engine_parallel_sampling_tail_copies_total.get());
+  }
   if (kv_offload_on.load(std::memory_order_relaxed)) {
     line(o, "engine_prefix_cache_offload_spilled_pages_total", "Evicted KV pages copied out to the host tier", "counter",
          engine_prefix_cache_offload_spilled_pages_total.get());

@@ -106,6 +106,19 @@ class Metrics {
     if (dropped > 0) engine_prefix_cache_offload_dropped_pages_total.add(dropped);
     if (hit_tokens > 0) engine_prefix_cache_offload_hit_tokens_total.add(hit_tokens);
   }
+  // Parallel sampling (n > 1 of /v1/chat/completions), counted by the engine: requests, prompt tokens the sibling
+  // choices did not prefill again, partial last prompt pages copied for them.  Present in /metrics once an engine has
+  // reported a request with n > 1 (observe_parallel_sampling); a server that never sees one shows what it showed.
+  Counter engine_parallel_sampling_requests_total;
+  Counter engine_parallel_sampling_shared_tokens_total;
+  Counter engine_parallel_sampling_tail_copies_total;
+  std::atomic<bool> parallel_sampling_on{false};
+  void observe_parallel_sampling(double requests, double shared_tokens, double tail_copies) {
+    parallel_sampling_on.store(true, std::memory_order_relaxed);
+    if (requests > 0) engine_parallel_sampling_requests_total.add(requests);
+    if (shared_tokens > 0) engine_parallel_sampling_shared_tokens_total.add(shared_tokens);
+    if (tail_copies > 0) engine_parallel_sampling_tail_copies_total.add(tail_copies);
+  }
   void observe_prefix_cache(double queries, double hits, double evictions) {
     prefix_cache_on.store(true, std::memory_order_relaxed);
     if (queries > 0) engine_prefix_cache_queries_total.add(queries);

@@ -53,6 +53,7 @@ py::dict request_dict(const ChatRequest& r) {
   d["guide_json"] = r.guide_json;  // response_format json_object
   d["guide_schema"] = r.guide_schema;  // `guide` is a lowered JSON Schema (guided_json / json_schema): the wide class
   d["from_edge"] = r.from_edge;
+  d["n"] = r.n;  // choices of this prompt (parallel sampling; 1 unless /v1/chat/completions asked for more)
   d["messages"] = r.messages_json;
   return d;
 }
@@ -81,6 +82,7 @@ class Runtime {
     c.dedupe_window_s = geti("dedupe_window_s", c.dedupe_window_s);
     c.keepalive_ms = geti("keepalive_ms", c.keepalive_ms);
     c.first_token_timeout_ms = geti("first_token_timeout_ms", c.first_token_timeout_ms);
+    c.max_choices = geti("max_choices", c.max_choices);
     c.max_pending_bytes = (size_t)geti("max_pending_bytes", (int)c.max_pending_bytes);
     c.flow_high_water = (size_t)geti("flow_high_water", (int)c.flow_high_water);
     c.socket_sndbuf = geti("socket_sndbuf", c.socket_sndbuf);
@@ -284,9 +286,10 @@ class DpWorkerPy {
     else w_->bye();
   }
   void observe(double step_s, double batch, double kv_free, double active, const std::vector<double>& ttft,
-               const std::vector<double>& itl, const std::vector<double>& host, const std::vector<double>& prefix) {
+               const std::vector<double>& itl, const std::vector<double>& host, const std::vector<double>& prefix,
+               const std::vector<double>& fork) {
     py::gil_scoped_release nogil;
-    w_->stats(step_s, batch, kv_free, active, ttft, itl, host, prefix);
+    w_->stats(step_s, batch, kv_free, active, ttft, itl, host, prefix, fork);
   }
   void set_vocab(const std::vector<std::string>&) {}  // text is resolved by the router
 
@@ -411,7 +414,7 @@ PYBIND11_MODULE(_dsse_runtime, m) {
       .def("set_ready", &DpWorkerPy::set_ready)
       .def("observe", &DpWorkerPy::observe, py::arg("step_s"), py::arg("batch"), py::arg("kv_free"), py::arg("active"),
            py::arg("ttft"), py::arg("itl"), py::arg("host") = std::vector<double>{},
-           py::arg("prefix") = std::vector<double>{})
+           py::arg("prefix") = std::vector<double>{}, py::arg("fork") = std::vector<double>{})
       .def("set_vocab", &DpWorkerPy::set_vocab);
   m.def("dp_ring_name", &dp_ring_name);
 
@@ -465,6 +468,10 @@ PYBIND11_MODULE(_dsse_runtime, m) {
   m.def("observe_prefix_cache", [](double queries, double hits, double evictions) {
     metrics().observe_prefix_cache(queries, hits, evictions);
   }, py::arg("queries"), py::arg("hits"), py::arg("evictions"));
+  // parallel sampling: deltas since the last call (called only once a request with n > 1 was seen)
+  m.def("observe_parallel_sampling", [](double requests, double shared_tokens, double tail_copies) {
+    metrics().observe_parallel_sampling(requests, shared_tokens, tail_copies);
+  }, py::arg("requests"), py::arg("shared_tokens"), py::arg("tail_copies"));
   m.def("observe_kv_offload", [](double spilled, double restored, double dropped, double hit_tokens) {
     metrics().observe_kv_offload(spilled, restored, dropped, hit_tokens);
   });

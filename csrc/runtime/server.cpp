@@ -580,12 +580,24 @@ struct Conn {
   // OpenAI chat completions (vLLM-compatible): frames are re-encoded as chat.completion chunks
   bool openai = false;
   bool oa_stream = true;
-  std::string oa_model, oa_text;
-  std::string oa_logprobs;  // non-stream completion with logprobs: the entries so far, comma-separated
+  std::string oa_model;
   bool oa_want_logprobs = false;
-  bool oa_lp_missing = false;  // a counted token came without an entry (stub / relay edge / replaced by the gate)
   int64_t oa_created = 0;
-  int oa_count = 0, oa_max_tokens = -1;
+  int oa_max_tokens = -1;
+  // per choice (`n` of them; one unless the request asked for more).  Choice i's frames arrive on the subject of
+  // choice_conversation_id(conv_id, i): the frame's conversation id selects the entry.
+  struct OaChoice {
+    int count = 0;          // completion tokens delivered
+    std::string text;       // non-stream: the content so far
+    std::string logprobs;   // non-stream completion with logprobs: the entries so far, comma-separated
+    bool lp_missing = false;  // a counted token came without an entry (stub / relay edge / replaced by the gate)
+    bool done = false;
+    std::string finish;     // finish_reason once done
+  };
+  std::vector<OaChoice> oa_choices;
+  std::vector<std::string> oa_ids;  // subjects of choices 1.. (empty for n = 1)
+  int oa_left = 0;                  // choices that have not ended
+  int oa_prompt_tokens = -1, oa_cached = -1;  // usage: the prompt once; cached_tokens as reported for choice 0
   // RESP
   bool resp_pubsub = false;
   std::vector<std::string> resp_channels, resp_patterns;
@@ -665,7 +677,8 @@ class IoThread {
   void deliver_token(Conn& c, const FramePtr& f);
   void handle_openai(Conn& c, HttpRequest& req);
   void deliver_openai(Conn& c, const FramePtr& f);
-  void finish_openai(Conn& c, const char* finish_reason, int prompt_tokens = -1, int cached_tokens = -1);
+  void finish_openai(Conn& c, int idx, const char* finish_reason, int prompt_tokens = -1, int cached_tokens = -1);
+  void abort_openai(Conn& c);  // every choice still running ends with finish_reason "abort"
   void flush_out(Conn& c);
   void close_conn(Conn& c);
   void drain_outbox();
@@ -795,12 +808,15 @@ void IoThread::flush_out(Conn& c) {
   if (pit != pending_.end()) pit->second->store(pend, std::memory_order_relaxed);
   const size_t hw = srv_.config().flow_high_water;
   if (hw && c.sse && c.sink) {
+    // (a connection with several choices pauses and resumes all of them together: they share its output queue)
     if (!c.congested && pend > hw) {
       c.congested = true;
       srv_.flow_update(c.conv_id, +1);
+      for (const auto& id : c.oa_ids) srv_.flow_update(id, +1);
     } else if (c.congested && pend < hw / 4) {
       c.congested = false;
       srv_.flow_update(c.conv_id, -1);
+      for (const auto& id : c.oa_ids) srv_.flow_update(id, -1);
     }
   }
   const bool ww = c.out_off < c.out.size();
@@ -850,13 +866,19 @@ void IoThread::end_sse(Conn& c, bool write_terminator) {
   if (!c.sse) return;
   c.sse = false;
   if (c.sink) {
-    srv_.bus().unsubscribe(c.conv_id, c.sink);
-    srv_.flow_update(c.conv_id, c.congested ? -1 : 0);
+    auto leave = [&](const std::string& id) {
+      srv_.bus().unsubscribe(id, c.sink);
+      srv_.flow_update(id, c.congested ? -1 : 0);
+      if (c.chat_mode && !srv_.bus().conversation_done(id) && srv_.bus().subscriber_count(id) == 0)
+        srv_.note_cancel(id);
+    };
+    leave(c.conv_id);
+    for (const auto& id : c.oa_ids) leave(id);  // every choice of the request: a disconnect cancels them all
     c.congested = false;
-    if (c.chat_mode && !srv_.bus().conversation_done(c.conv_id) && srv_.bus().subscriber_count(c.conv_id) == 0)
-      srv_.note_cancel(c.conv_id);
     c.sink.reset();
   }
+  if (!c.oa_ids.empty()) srv_.unregister_choices(c.conv_id);
+  c.oa_ids.clear();
   c.held.clear();
   c.openai = false;
   metrics().sse_active_connections.add(-1);
@@ -1017,7 +1039,20 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
     }
     return (int64_t)v;
   };
-  if (num("n", 1) != 1) return bad(400, "only n = 1 is supported");
+  // n: choices of this prompt (parallel sampling).  A JSON null is "not given"; anything but an integer in [1, 16],
+  // or more than the engine has decode slots, is refused
+  int n_choices = 1;
+  {
+    auto ni = o.find("n");
+    if (ni != o.end() && ni->second.kind != JsonValue::kNull) {
+      const double v = ni->second.kind == JsonValue::kNumber ? ni->second.num : NAN;
+      if (!(v >= 1 && v <= 16) || v != std::floor(v)) return bad(400, "n must be an integer in [1, 16]");
+      n_choices = (int)v;
+      if (n_choices > srv_.config().max_choices)
+        return bad(400, "n = " + std::to_string(n_choices) + " exceeds the engine's MAX_BATCH (at most " +
+                            std::to_string(srv_.config().max_choices) + " choices per request)");
+    }
+  }
   int64_t max_tokens = int_param("max_tokens", 1, 1 << 20);
   if (max_tokens < 0) max_tokens = int_param("max_completion_tokens", 1, 1 << 20);
   const int64_t top_k = int_param("top_k", -1, 1 << 20);
@@ -1069,16 +1104,18 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
     r.logprobs = want ? top : -1;
   }
   r.from_edge = true;
+  r.n = n_choices;
   auto mo = o.find("model");
   c.openai = true;
   c.oa_stream = stream;
   c.oa_model = (mo != o.end() && mo->second.kind == JsonValue::kString && !mo->second.str.empty()) ? mo->second.str : model;
   c.oa_created = (int64_t)time(nullptr);
-  c.oa_count = 0;
   c.oa_max_tokens = r.max_tokens;
-  c.oa_text.clear();
-  c.oa_logprobs.clear();
-  c.oa_lp_missing = false;
+  c.oa_choices.assign((size_t)n_choices, Conn::OaChoice{});
+  c.oa_left = n_choices;
+  c.oa_prompt_tokens = c.oa_cached = -1;
+  c.oa_ids.clear();
+  for (int i = 1; i < n_choices; ++i) c.oa_ids.push_back(choice_conversation_id(conv, i));
   c.oa_want_logprobs = r.logprobs >= 0;
   // subscribe before submitting, as POST /chat does
   auto sink = std::make_shared<ConnSink>();
@@ -1089,11 +1126,18 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   c.sink = sink;
   srv_.bus().subscribe(conv, sink, -1, nullptr);
   srv_.flow_update(conv, 0);
+  if (!c.oa_ids.empty()) srv_.register_choices(conv, c.oa_ids);
+  for (const auto& id : c.oa_ids) {  // every choice's subject, before the request leaves
+    srv_.bus().subscribe(id, sink, -1, nullptr);
+    srv_.flow_update(id, 0);
+  }
   if (stream) {
-    const std::string first = "data: {\"id\":" + json_quote(conv) + ",\"object\":\"chat.completion.chunk\",\"created\":" +
-                              std::to_string(c.oa_created) + ",\"model\":" + json_quote(c.oa_model) +
-                              ",\"choices\":[{\"index\":0,\"delta\":{\"role\":\"assistant\",\"content\":\"\"},"
-                              "\"logprobs\":null,\"finish_reason\":null}]}\n\n";
+    std::string first;  // one role chunk per choice
+    for (int i = 0; i < n_choices; ++i)
+      first += "data: {\"id\":" + json_quote(conv) + ",\"object\":\"chat.completion.chunk\",\"created\":" +
+               std::to_string(c.oa_created) + ",\"model\":" + json_quote(c.oa_model) + ",\"choices\":[{\"index\":" +
+               std::to_string(i) + ",\"delta\":{\"role\":\"assistant\",\"content\":\"\"},"
+               "\"logprobs\":null,\"finish_reason\":null}]}\n\n";
     start_sse(c, conv, true, -1, first, nullptr);
   } else {  // buffered: no HTTP response until the completion is done
     c.sse = true;
@@ -1112,6 +1156,16 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
 void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
   TokenMessage m;
   if (!parse_token_message(f->json(), m)) return;
+  // the choice this frame belongs to: the connection's own id is choice 0, id + "-c" + i is choice i
+  int idx = 0;
+  if (f->conversation_id != c.conv_id) {
+    idx = -1;
+    for (size_t i = 0; i < c.oa_ids.size(); ++i)
+      if (c.oa_ids[i] == f->conversation_id) idx = (int)i + 1;
+  }
+  if (idx < 0 || (size_t)idx >= c.oa_choices.size()) return;
+  Conn::OaChoice& ch = c.oa_choices[(size_t)idx];
+  if (ch.done) return;
   if (f->done) {
     // vLLM's finish_reason: the engine's own reason when it sent one (EOS = stop; max_tokens or the context
     // limit = length; cancelled = abort), else from the terminal token and the count
@@ -1119,20 +1173,20 @@ void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
     if (f->finish == kFinishStop) reason = "stop";
     else if (f->finish == kFinishLength) reason = "length";
     else if (f->finish == kFinishAbort || m.token == "[ERROR]" || m.token == "[BLOCKED]" || m.token == "[KILLED]") reason = "abort";
-    else reason = c.oa_max_tokens > 0 && c.oa_count >= c.oa_max_tokens ? "length" : "stop";
-    return finish_openai(c, reason, f->prompt_tokens, f->cached_tokens);
+    else reason = c.oa_max_tokens > 0 && ch.count >= c.oa_max_tokens ? "length" : "stop";
+    return finish_openai(c, idx, reason, f->prompt_tokens, f->cached_tokens);
   }
   c.got_first = true;
-  ++c.oa_count;
+  ++ch.count;
   metrics().sse_messages_delivered_total.inc();
   const bool has_lp = c.oa_want_logprobs && !f->logprobs.empty();
   if (!c.oa_stream) {
-    c.oa_text += m.token;
+    ch.text += m.token;
     if (has_lp) {
-      if (!c.oa_logprobs.empty()) c.oa_logprobs += ',';
-      c.oa_logprobs += f->logprobs;
+      if (!ch.logprobs.empty()) ch.logprobs += ',';
+      ch.logprobs += f->logprobs;
     } else {
-      c.oa_lp_missing = true;
+      ch.lp_missing = true;
     }
     return;
   }
@@ -1145,49 +1199,71 @@ void IoThread::deliver_openai(Conn& c, const FramePtr& f) {
   json_append_string(ev, c.conv_id);
   ev += ",\"object\":\"chat.completion.chunk\",\"created\":" + std::to_string(c.oa_created) + ",\"model\":";
   json_append_string(ev, c.oa_model);
-  ev += ",\"choices\":[{\"index\":0,\"delta\":{\"content\":";
+  ev += ",\"choices\":[{\"index\":" + std::to_string(idx) + ",\"delta\":{\"content\":";
   json_append_string(ev, m.token);
   if (has_lp) ev += "},\"logprobs\":{\"content\":[" + f->logprobs + "]},\"finish_reason\":null}]}\n\n";
   else ev += "},\"logprobs\":null,\"finish_reason\":null}]}\n\n";
   write_sse_bytes(c, ev);
 }
 
-void IoThread::finish_openai(Conn& c, const char* finish_reason, int prompt_tokens, int cached_tokens) {
-  if (!c.sse) return;
-  const int pt = std::max(0, prompt_tokens);
+void IoThread::abort_openai(Conn& c) {
+  for (size_t i = 0; i < c.oa_choices.size() && c.sse; ++i)
+    if (!c.oa_choices[i].done) finish_openai(c, (int)i, "abort");
+}
+
+// Choice `idx` has ended.  Streaming: its finish chunk goes out now, and `data: [DONE]` behind the last choice's.
+// Buffered: nothing is written until the last choice ends; then one body with every choice, ordered by index.
+// usage: the prompt counted once, completion_tokens summed over the choices, cached_tokens as choice 0 reported it.
+void IoThread::finish_openai(Conn& c, int idx, const char* finish_reason, int prompt_tokens, int cached_tokens) {
+  if (!c.sse || idx < 0 || (size_t)idx >= c.oa_choices.size() || c.oa_choices[(size_t)idx].done) return;
+  c.oa_choices[(size_t)idx].done = true;
+  c.oa_choices[(size_t)idx].finish = finish_reason;
+  c.oa_prompt_tokens = std::max(c.oa_prompt_tokens, prompt_tokens);
+  if (idx == 0) c.oa_cached = cached_tokens;
+  const bool last = --c.oa_left <= 0;
+  const int pt = std::max(0, c.oa_prompt_tokens);
+  int completion = 0;
+  for (const auto& ch : c.oa_choices) completion += ch.count;
   const std::string head = "{\"id\":" + json_quote(c.conv_id) + ",\"object\":\"chat.completion" +
                            std::string(c.oa_stream ? ".chunk" : "") + "\",\"created\":" + std::to_string(c.oa_created) +
-                           ",\"model\":" + json_quote(c.oa_model) + ",\"choices\":[{\"index\":0,";
+                           ",\"model\":" + json_quote(c.oa_model) + ",\"choices\":[";
   const std::string usage = "\"usage\":{\"prompt_tokens\":" + std::to_string(pt) + ",\"total_tokens\":" +
-                            std::to_string(pt + c.oa_count) + ",\"completion_tokens\":" + std::to_string(c.oa_count) +
+                            std::to_string(pt + completion) + ",\"completion_tokens\":" + std::to_string(completion) +
                             // prefix caching on (the engine then sends a count >= 0): vLLM's prompt_tokens_details;
                             // off: no such key, and the stream's last chunk carries no usage, as before
-                            (cached_tokens >= 0 ? ",\"prompt_tokens_details\":{\"cached_tokens\":" +
-                                                      std::to_string(cached_tokens) + "}"
-                                                : std::string()) +
+                            (c.oa_cached >= 0 ? ",\"prompt_tokens_details\":{\"cached_tokens\":" +
+                                                    std::to_string(c.oa_cached) + "}"
+                                              : std::string()) +
                             "}";
   if (c.oa_stream) {
-    std::string ev = "data: " + head + "\"delta\":{},\"logprobs\":null,\"finish_reason\":\"" + finish_reason +
-                     "\",\"stop_reason\":null}]" + (cached_tokens >= 0 ? "," + usage : std::string()) +
-                     "}\n\ndata: [DONE]\n\n";
+    std::string ev = "data: " + head + "{\"index\":" + std::to_string(idx) +
+                     ",\"delta\":{},\"logprobs\":null,\"finish_reason\":\"" + finish_reason +
+                     "\",\"stop_reason\":null}]" + (last && c.oa_cached >= 0 ? "," + usage : std::string()) + "}\n\n";
+    if (!last) return write_sse_bytes(c, ev);
+    ev += "data: [DONE]\n\n";
     append_chunk(c.out, ev.data(), ev.size());
     end_sse(c, true);
     return;
   }
+  if (!last) return;
   const bool ka = c.keep_alive;
-  std::string body = head + "\"message\":{\"role\":\"assistant\",\"content\":" + json_quote(c.oa_text) +
-                     ",\"tool_calls\":[]},\"logprobs\":" +
-                     // one entry per completion token or none at all: a token without one (the stub generator, an
-                     // engine behind a relay edge, a frame the inspection gate replaced) leaves null, as the stream does
-                     (c.oa_want_logprobs && !c.oa_lp_missing && !c.oa_logprobs.empty()
-                          ? "{\"content\":[" + c.oa_logprobs + "]}" : std::string("null")) +
-                     ",\"finish_reason\":\"" + finish_reason +
-                     "\",\"stop_reason\":null}]," + usage + "}";
+  std::string body = head;
+  for (size_t i = 0; i < c.oa_choices.size(); ++i) {
+    const auto& ch = c.oa_choices[i];
+    body += std::string(i ? ",{" : "{") + "\"index\":" + std::to_string(i) +
+            ",\"message\":{\"role\":\"assistant\",\"content\":" + json_quote(ch.text) +
+            ",\"tool_calls\":[]},\"logprobs\":" +
+            // one entry per completion token or none at all: a token without one (the stub generator, an
+            // engine behind a relay edge, a frame the inspection gate replaced) leaves null, as the stream does
+            (c.oa_want_logprobs && !ch.lp_missing && !ch.logprobs.empty()
+                 ? "{\"content\":[" + ch.logprobs + "]}" : std::string("null")) +
+            ",\"finish_reason\":\"" + ch.finish + "\",\"stop_reason\":null}";
+  }
+  body += "]," + usage + "}";
   // buffered mode never wrote headers: close the pseudo-SSE session, then send one JSON response (and close
   // the connection after it when the client asked for Connection: close)
   end_sse(c, false);
-  c.oa_text.clear();
-  c.oa_logprobs.clear();
+  c.oa_choices.clear();
   write_raw(c, simple_response(200, body, "application/json", ka));
   if (!ka) {
     c.close_after_write = true;
@@ -1269,7 +1345,7 @@ void IoThread::timers() {
     }
     if (!c.sse) continue;
     if (c.openai) {
-      if (!c.got_first && now >= c.first_deadline_mono) finish_openai(c, "abort");
+      if (!c.got_first && now >= c.first_deadline_mono) abort_openai(c);
       else if (c.oa_stream && now - c.last_write_mono >= ka) write_sse_bytes(c, ": keep-alive\n\n");
       if (c.close_after_write && c.out_off >= c.out.size()) to_close.push_back(c.fd);
       continue;
@@ -1786,9 +1862,33 @@ void Server::note_cancel(const std::string& conv_id) {
   cancels_.push_back(conv_id);
 }
 
+void Server::register_choices(const std::string& conv_id, const std::vector<std::string>& sibling_ids) {
+  std::lock_guard<std::mutex> g(choices_mu_);
+  choices_[conv_id] = sibling_ids;
+}
+
+void Server::unregister_choices(const std::string& conv_id) {
+  std::lock_guard<std::mutex> g(choices_mu_);
+  choices_.erase(conv_id);
+}
+
 bool Server::kill_conversation(const std::string& conv_id, const std::string& token, const std::string& why) {
-  if (conv_id.empty() || !bus_->terminate(conv_id, token, kFinishAbort)) return false;
-  note_cancel(conv_id);
+  if (conv_id.empty()) return false;
+  // a request with several choices is killed whole: every choice that still runs gets the terminal token, also when
+  // choice 0 itself has already ended (its subject is done then, and terminate() has nothing to do there)
+  std::vector<std::string> ids{conv_id};
+  {
+    std::lock_guard<std::mutex> g(choices_mu_);
+    auto it = choices_.find(conv_id);
+    if (it != choices_.end()) ids.insert(ids.end(), it->second.begin(), it->second.end());
+  }
+  bool any = false;
+  for (const auto& id : ids) {
+    if (!bus_->terminate(id, token, kFinishAbort)) continue;
+    note_cancel(id);
+    any = true;
+  }
+  if (!any) return false;
   log_json(LogLevel::kWarn, "conversation killed",
            "\"conversation_id\":" + json_quote(conv_id) + ",\"token\":" + json_quote(token) + ",\"reason\":" + json_quote(why));
   return true;
@@ -2194,12 +2294,19 @@ void StubEngine::run() {
   std::mt19937 rng{std::random_device{}()};
   while (!stop_.load()) {
     for (auto& r : server_.requests().pop(256, live.empty() ? 50 : 0)) {
-      Item it;
-      it.n = r.max_tokens > 0 ? r.max_tokens : tokens_;
-      it.req = std::move(r);
-      it.due_ns = mono_ns();
-      live.push_back(std::move(it));
-      metrics().active_chats.add(1);
+      for (int ci = r.n - 1; ci >= 0; --ci) {  // one stream per choice, under its own subject
+        Item it;
+        it.n = r.max_tokens > 0 ? r.max_tokens : tokens_;
+        if (ci) {
+          it.req = r;
+          it.req.conversation_id = choice_conversation_id(r.conversation_id, ci);
+        } else {
+          it.req = std::move(r);
+        }
+        it.due_ns = mono_ns();
+        live.push_back(std::move(it));
+        metrics().active_chats.add(1);
+      }
     }
     int64_t now = mono_ns(), next_due = now + 5000000;
     std::vector<FramePtr> batch;

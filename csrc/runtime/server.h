@@ -71,6 +71,8 @@ struct ServerConfig {
   size_t replay_max = 4096;
   int retention_s = 300;
   std::string ui_html;  // served at GET / when non-empty
+  // POST /v1/chat/completions: the largest `n` (choices per request) it accepts, min(16, the engine's decode slots)
+  int max_choices = 16;
 };
 
 // Chat request handed to the engine (or the stub generator).
@@ -103,10 +105,19 @@ struct ChatRequest {
   bool guide_schema = false;
   bool guide_json = false;  // response_format {"type":"json_object"}: JSON mode (never together with `guide`)
   bool from_edge = false;   // submitted by the edge /chat (a subscriber exists)
+  // parallel sampling (POST /v1/chat/completions `n`): this many choices of one prompt.  Choice 0 streams under
+  // conversation_id, choice i under conversation_id + "-c" + i; the engine prefills the prompt once and forks its KV
+  // pages (choice_conversation_id below; LLMEngine.add_request).  POST /chat has no n.
+  int n = 1;
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON
   // [{"role":..,"content":..},..]; empty = `message` is a single user turn
   std::string messages_json;
 };
+
+// Conversation id (= bus subject) of choice i of a request: the id itself for choice 0.
+inline std::string choice_conversation_id(const std::string& conv_id, int i) {
+  return i <= 0 ? conv_id : conv_id + "-c" + std::to_string(i);
+}
 
 class RequestQueue {
  public:
@@ -156,6 +167,11 @@ class Server {
   // Kill a conversation (chat.<id>.control, chat.control.kill, or an inspection verdict): subscribers get a
   // terminal `token` frame (done) and the engine a cancellation.  False if it had already ended.
   bool kill_conversation(const std::string& conv_id, const std::string& token, const std::string& why);
+  // A request with several choices (POST /v1/chat/completions n > 1): the subjects of choices 1.., recorded under
+  // choice 0's conversation id while the request's connection is open, so that a kill of that id ends them all --
+  // whatever choice 0's own state -- and nothing is guessed from names.
+  void register_choices(const std::string& conv_id, const std::vector<std::string>& sibling_ids);
+  void unregister_choices(const std::string& conv_id);
   // A remote inline / hybrid inspection gate holds frames before fan-out (per-connection inspection off).
   bool remote_inspection() const { return gate_ != nullptr; }
   // A subscriber of `conv_id` crossed the high-water mark (+1), drained (-1), or the subscriber set
@@ -186,6 +202,8 @@ class Server {
   std::atomic<int> vocab_size_{0};
   std::atomic<uint64_t> next_req_{1};
   std::mutex cancel_mu_;
+  std::mutex choices_mu_;
+  std::unordered_map<std::string, std::vector<std::string>> choices_;  // choice 0's id -> its siblings' ids
   std::vector<std::string> cancels_;
   std::mutex flow_mu_;
   std::unordered_map<std::string, std::pair<int, bool>> flow_;  // congested subscribers, paused

@@ -154,6 +154,8 @@ class Sequence:
     cached_tokens: int = -1     # prefix caching: prompt tokens served from resident pages at its FIRST admission
     hashes: list = field(default_factory=list)  # prefix caching: chain hashes of its full pages, prompt pages first
     published: int = 0          # prefix caching: its leading pages that are shared or were offered to the index
+    parent: object = None       # parallel sampling: choice 0 of its request, whose prompt pages it forks at its first
+                                # admission (choices 1..n-1 only; cleared once used or once it took the plain path)
 
 
 class EngineFault(RuntimeError):
@@ -411,7 +413,10 @@ class LLMEngine:
         self.stats = {"steps": 0, "decode_steps": 0, "mixed_steps": 0, "prefill_tokens": 0, "tokens": 0,
                       "last_step_s": 0.0, "pauses": 0, "preemptions": 0, "compactions": 0, "host_s": 0.0, "wait_s": 0.0,
                       # prefix caching: prompt tokens looked up / served from resident pages (admissions), pages evicted
-                      "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0}
+                      "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0,
+                      # parallel sampling (add_request n > 1): requests / prompt tokens the siblings did not prefill
+                      # again / partial last prompt pages copied for them (kv_pages_copy)
+                      "fork_requests": 0, "fork_shared_tokens": 0, "fork_tail_copies": 0}
         if self.offload is not None:
             # host tier: pages copied out at eviction / evicted with their content already there / evicted with no
             # free staging record or host slot (content lost) / copied back at admission, and the tokens those held
@@ -420,6 +425,12 @@ class LLMEngine:
         # admission keeps this many pages free for running sequences to grow into (vLLM's 1% watermark)
         self.watermark = max(1, runner.kv.num_blocks // 100)
         self._bt_new: list = []  # (sequence, page index, block) appended since the last upload
+        # parallel sampling: conversation id of choice 0 -> ids of its request's choices that are still alive (abort
+        # by that id ends them all), and each of those ids -> choice 0's; (src, dst) tail-page copies of the siblings
+        # admitted in this step, launched together before the step's passes
+        self._groups: dict = {}
+        self._group_of: dict = {}
+        self._fork_pairs: list = []
         self._pending: list = []  # events raised between steps (aborts of queued requests), returned by the next
         self.on_ttft = None
         self.ttft_trace = None  # a list: (arrival, queued, admitted, first token) ns per sequence
@@ -469,9 +480,40 @@ class LLMEngine:
         return next(self._rid)
 
     def add_request(self, conversation_id: str, prompt: list, params: SamplingParams | None = None,
-                    arrival_ns: int | None = None, rid: int | None = None) -> Sequence:
+                    arrival_ns: int | None = None, rid: int | None = None, n: int = 1, choice_ids=None):
         """Queue a request.  `rid` (a TP leader's request id, replayed on its followers) seeds the sampling RNG
-        when the params carry no seed, so it must be the same on every rank of a TP group."""
+        when the params carry no seed, so it must be the same on every rank of a TP group.
+
+        n > 1 (parallel sampling) queues n sequences, the choices of one request, and returns them as a list: choice 0
+        under `conversation_id`, choice i under f"{conversation_id}-c{i}" (or `choice_ids[i]`), with consecutive rids
+        rid .. rid + n - 1.  With a seed, choice i samples with seed + i (the draw is per (seed, position): equal seeds
+        would give equal siblings), so choice 0 is the same request with n = 1; without one the rid-derived seeds
+        differ already.  Choices 1.. wait behind choice 0 and fork its prompt's KV pages once its whole prompt is
+        enqueued (_admit); when choice 0 is gone by then they prefill on their own."""
+        n = int(n)
+        if n != 1:
+            if not 1 <= n <= self.r.max_batch:
+                raise ValueError(f"n must be in [1, {self.r.max_batch}] (the engine's max_batch), got {n}")
+            ids = [conversation_id] + [f"{conversation_id}-c{i}" for i in range(1, n)] if choice_ids is None \
+                else list(choice_ids)
+            if len(ids) != n or ids[0] != conversation_id or len(set(ids)) != n:
+                raise ValueError("choice_ids must be n distinct ids, the first the conversation id")
+            p = params or self.default_params
+            first = rid if rid is not None else next(self._rid)
+            seqs = []
+            for i, cid in enumerate(ids):
+                pi = p if p.seed is None or i == 0 else SamplingParams(**{**p.__dict__, "seed": int(p.seed) + i})
+                r_i = first + i if rid is not None or i == 0 else next(self._rid)
+                s = self.add_request(cid, prompt, pi, arrival_ns=arrival_ns, rid=r_i)
+                if i:
+                    s.parent = seqs[0]
+                seqs.append(s)
+            assert [s.rid for s in seqs] == list(range(first, first + n)), "parallel sampling: rids must be consecutive"
+            self._groups[conversation_id] = set(ids)
+            for cid in ids:
+                self._group_of[cid] = conversation_id
+            self.stats["fork_requests"] += 1
+            return seqs
         p = params or self.default_params
         if p.json_object:
             if p.guide is not None:
@@ -494,7 +536,16 @@ class LLMEngine:
         self.by_conv[conversation_id] = s
         return s
 
-    def abort(self, conversation_id: str) -> bool:
+    def abort(self, conversation_id: str, choices: bool = True) -> bool:
+        """Abort a conversation.  The id of a request with n > 1 (its choice 0's) ends every choice still alive;
+        choices=False ends that one sequence only (a stop string matched in choice 0's text)."""
+        group = self._groups.get(conversation_id) if choices else None
+        if group is not None:
+            hit = [self._abort_one(c) for c in sorted(group)]
+            return any(hit)
+        return self._abort_one(conversation_id)
+
+    def _abort_one(self, conversation_id: str) -> bool:
         s = self.by_conv.get(conversation_id)
         if s is None or s.state == "finished":
             return False
@@ -835,8 +886,24 @@ class LLMEngine:
             if s.params.guide is not None and (s.params.guide, s.params.guide_schema) not in self._guide_idx and \
                     all(self._guide_refs[i] > 0 for i in self._guide_pool(s.params.guide_schema)):
                 return  # its pattern is not resident and every pool entry is in use: it waits, as for KV pages
+            # parallel sampling: a sibling whose parent (choice 0) holds a slot with its whole prompt enqueued is
+            # admitted like a prefix hit of len(prompt) - 1 tokens on the parent's own pages; it waits while the parent
+            # is still prefilling, and takes the plain path below when the parent is gone (finished, aborted, preempted)
+            par, s.parent = s.parent, None
+            if par is not None:
+                if par.state == "prefill" and not par.aborted and par.prefilled < len(par.prompt):
+                    s.parent = par
+                    return
+                if not (par.state in ("prefill", "decode") and par.slot >= 0 and self.slots[par.slot] is par
+                        and not par.aborted and par.base == 0 and par.prefilled == len(par.prompt)
+                        and len(par.prompt) == len(s.prompt) and len(par.blocks) >= blocks_needed(len(s.prompt))):
+                    par = None
+            nshared = (len(s.prompt) - 1) // PAGE if par is not None else 0
             hits, run, host = [], None, []
-            if self.prefix_cache:
+            if par is not None:
+                if self.prefix_cache and not s.hashes:
+                    s.hashes = page_hashes(s.prompt)
+            elif self.prefix_cache:
                 # the resident leading pages of the prompt minus its last token: at least one token is always
                 # prefilled, so the first token is sampled by the ordinary last-chunk path.  (Hashed once; looked up
                 # on every attempt while it waits: the index changes between steps.)
@@ -852,9 +919,10 @@ class LLMEngine:
                     run, host = self.alloc.lookup_tiers(chain, max_host=self.offload.free_records())
                     hits = [b for b in run if b is not None]
             # pages to allocate: everything that is not resident, the host-tier hits' new HBM pages included
-            need = blocks_needed(len(s.prompt)) - len(hits)
+            need = blocks_needed(len(s.prompt)) - (len(hits) if par is None else nshared)
             idle = not any(x is not None for x in self.slots)
             if need > self.alloc.num_free - (0 if idle else self.watermark):
+                s.parent = par  # (a sibling that waits for pages still forks when they come)
                 if hits:
                     self.alloc.free(hits)  # it waits: the references go back (the pages stay indexed)
                 for _, slot in host:
@@ -865,7 +933,19 @@ class LLMEngine:
                     continue
                 return
             self.waiting.popleft()
-            if not host:
+            if par is not None:
+                # fork: one more reference on the parent's full prompt pages (never written again by anyone), one
+                # private page for the rest.  When the last prompt token is not the first of its page, that page starts
+                # as a copy of the parent's: the copy is enqueued with this step's others, before its passes, so stream
+                # order puts it behind the parent's prompt writes and ahead of this sibling's first chunk.
+                hits = self.alloc.fork(par.blocks[:nshared])
+                new = self.alloc.allocate(need)
+                s.blocks = hits + new
+                if (len(s.prompt) - 1) % PAGE:
+                    self._fork_pairs.append((par.blocks[nshared], new[0]))
+                    self.stats["fork_tail_copies"] += 1
+                self.stats["fork_shared_tokens"] += len(s.prompt) - 1
+            elif not host:
                 s.blocks = hits + self.alloc.allocate(need)
             else:
                 # restore: the first new pages take the host-tier hits' places.  The allocation may have evicted
@@ -885,14 +965,16 @@ class LLMEngine:
                 self.stats["offload_hit_tokens"] += PAGE * len(host)
             s.slot = free
             s.state = "prefill"
-            s.prefilled = PAGE * len(hits)  # its chunks start here: it writes private pages only
+            # its chunks start here: it writes private pages only (a forked sibling: its last prompt token alone)
+            s.prefilled = PAGE * len(hits) if par is None else len(s.prompt) - 1
             s.published = len(hits)
             s.decode_enqueued = 0
             if self.prefix_cache:
                 if s.cached_tokens < 0:  # what the client is told: the first admission's hit, not a re-prefill's
                     s.cached_tokens = min(s.prefilled, s.orig_len)
-                self.stats["prefix_queries"] += len(s.prompt)
-                self.stats["prefix_hit_tokens"] += s.prefilled
+                if par is None:  # (a fork is not a lookup: it has its own counters)
+                    self.stats["prefix_queries"] += len(s.prompt)
+                    self.stats["prefix_hit_tokens"] += s.prefilled
                 self.stats["prefix_evictions"] = self.alloc.evictions
             self.slots[s.slot] = s
             self._dirty_slots.add(s.slot)
@@ -922,6 +1004,12 @@ class LLMEngine:
                                                                       r.guide_eos))
             else:
                 r.set_guide(s.slot, -1, 0)  # (a no-op until a guided request has been seen)
+
+    def _copy_fork_tails(self):
+        """The tail pages of the siblings admitted in this step, in one launch on the compute stream (after the step's
+        spills were read out of the blocks it allocated, before its passes)."""
+        pairs, self._fork_pairs = self._fork_pairs, []
+        ops.kv_pages_copy(self.r.kv.k, self.r.kv.v, pairs)
 
     def _compact(self):
         """Move decoding sequences above the bucket their count needs into lower free / paused slots."""
@@ -1061,6 +1149,13 @@ class LLMEngine:
             s.blocks = []
         if self.by_conv.get(s.conversation_id) is s:
             del self.by_conv[s.conversation_id]
+        root = self._group_of.pop(s.conversation_id, None)
+        if root is not None:
+            live = self._groups.get(root)
+            if live is not None:
+                live.discard(s.conversation_id)
+                if not live:
+                    del self._groups[root]
 
     # ------------------------------------------------------------------ step
     def step(self, block: bool = True) -> list:
@@ -1081,6 +1176,8 @@ class LLMEngine:
         self._admit()
         # host tier: the pages this step's allocations evicted are copied out before the step that writes them
         self._drain_spills()
+        if self._fork_pairs:
+            self._copy_fork_tails()
         if not self.waiting:
             self._compact()
         t_a = time.perf_counter()
@@ -1096,7 +1193,7 @@ class LLMEngine:
         B = next(b for b in batch_buckets(r.max_batch) if b >= max(s.slot for s in dec) + 1) if dec else 0
         # a mixed step only when the chunks fit its captured graph (a starved prompt's big budget: separate passes)
         mixed = bool(chunks) and bool(dec) and self.mixed and self._mixed_fits(B, chunks)
-        if self.prefix_cache and self.debug_shared_writes:
+        if (self.prefix_cache or self.alloc.has_forks) and self.debug_shared_writes:
             self._check_write_pages(chunks, dec)
         if chunks:
             if not mixed:

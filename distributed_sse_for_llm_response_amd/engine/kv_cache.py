@@ -180,6 +180,11 @@ class BlockAllocator:
     is never written again.  With the flag off nothing below the free list is touched: the same pages in the same
     order as ever.
 
+    ``fork`` (parallel sampling: the choices of one request share their prompt's full pages) takes one more reference
+    on blocks that already have an owner, in either mode.  With the prefix cache on that is the per-page count; with
+    it off, a sparse table of the extra references, empty unless something was forked, so that ``free`` gives a block
+    back only when its last owner lets go of it.
+
     host_store (a HostPageStore, with prefix_cache=True only) adds the host tier: an evicted page's (block, hash) goes
     on a spill list that the engine drains (``take_spills``) and copies out before the page's new owner writes it, and
     ``lookup_tiers`` continues a hash chain from the index into the store.  Which pages are handed out, and in which
@@ -194,6 +199,7 @@ class BlockAllocator:
         self.host_store = host_store
         self._spills: list = []  # (block, hash) of pages evicted since take_spills, least recently used first
         self.evictions = 0
+        self._extra: dict = {}  # prefix_cache off: block -> references beyond the first (fork)
         if prefix_cache:
             self._ref = [0] * num_blocks
             self._index: dict = {}      # page hash -> block
@@ -230,6 +236,17 @@ class BlockAllocator:
     def free(self, blocks) -> None:
         blocks = list(blocks)
         if not self.prefix_cache:
+            if self._extra:  # a forked block loses one reference and stays with its other owners
+                kept = []
+                for b in blocks:
+                    n = self._extra.get(b)
+                    if n is None:
+                        kept.append(b)
+                    elif n > 1:
+                        self._extra[b] = n - 1
+                    else:
+                        del self._extra[b]
+                blocks = kept
             self._free.extend(reversed(blocks))
             return
         plain = []
@@ -244,6 +261,25 @@ class BlockAllocator:
                 else:
                     plain.append(b)
         self._free.extend(plain)  # (already reversed: the first of `blocks` is the next one allocated, as ever)
+
+    def fork(self, blocks) -> list:
+        """One more reference on each of `blocks`, which must have an owner already (parallel sampling: a sibling
+        shares its parent's full prompt pages).  Returns them; the caller gives them back with ``free`` like any
+        other block, and nobody writes them while they are shared (``is_shared``)."""
+        blocks = list(blocks)
+        if self.prefix_cache:
+            for b in blocks:
+                assert self._ref[b] > 0, f"KV page {b} forked without an owner"
+                self._ref[b] += 1
+        else:
+            for b in blocks:
+                self._extra[b] = self._extra.get(b, 0) + 1
+        return blocks
+
+    @property
+    def has_forks(self) -> bool:
+        """Prefix cache off: some block has more than one owner right now."""
+        return bool(self._extra)
 
     # ---- prefix cache -------------------------------------------------------------------------
     def lookup(self, hashes) -> list:
@@ -303,7 +339,9 @@ class BlockAllocator:
 
     def is_shared(self, block: int) -> bool:
         """More than one owner, or published (a later lookup may read it): it must never be written."""
-        return self.prefix_cache and (self._ref[block] > 1 or block in self._hash_of)
+        if not self.prefix_cache:
+            return block in self._extra
+        return self._ref[block] > 1 or block in self._hash_of
 
 
 def blocks_needed(num_tokens: int) -> int:

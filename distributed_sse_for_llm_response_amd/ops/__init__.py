@@ -513,6 +513,45 @@ def kv_pages_scatter(staging, blocks, k_cache, v_cache):
         ref.kv_pages_scatter(staging, dev, k_cache, v_cache)
 
 
+def kv_pages_copy(k_cache, v_cache, pairs):
+    """Page dst = page src for every (src, dst) of `pairs`, all layers, K and V, inside the paged cache (parallel
+    sampling: a sibling's private copy of its parent's partial last prompt page; csrc/kernels/kv_pages.hip).  `pairs` is
+    a host list of (src_block, dst_block), validated HERE before anything is launched: every index in [0, num_blocks),
+    each destination named once, and no destination also a source (one source may feed several destinations).  Every
+    page that is not a destination is untouched."""
+    if isinstance(pairs, torch.Tensor):
+        if pairs.is_cuda:
+            raise ValueError("pairs must be a host list or CPU tensor: its indices are validated before the launch")
+        pairs = pairs.tolist()
+    vals = []
+    for p in pairs:
+        if len(p) != 2:
+            raise ValueError("pairs: every entry is (src_block, dst_block)")
+        vals.append((int(p[0]), int(p[1])))
+    if k_cache.dim() != 5 or v_cache.dim() != 5 or k_cache.shape[:3] != v_cache.shape[:3]:
+        raise ValueError("k_cache / v_cache must be the 5-D paged caches of one shape")
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"cache dtypes {k_cache.dtype} / {v_cache.dtype} must agree")
+    num_blocks = k_cache.shape[1]
+    bad = [b for p in vals for b in p if not 0 <= b < num_blocks]
+    if bad:
+        raise ValueError(f"pairs: index {bad[0]} outside [0, {num_blocks})")
+    dsts = [d for _, d in vals]
+    if len(set(dsts)) != len(dsts):
+        raise ValueError("pairs: each destination page may be named once (duplicate destination)")
+    both = set(dsts) & {s for s, _ in vals}
+    if both:
+        raise ValueError(f"pairs: page {min(both)} is both a destination and a source")
+    if not vals:
+        return  # nothing is launched
+    host = torch.tensor(vals, dtype=torch.int32).view(-1, 2)
+    if _hip(k_cache):
+        dev = host.pin_memory().to(k_cache.device, non_blocking=True)
+        torch.ops.dsse.kv_pages_copy(k_cache, v_cache, dev)
+    else:
+        ref.kv_pages_copy(k_cache, v_cache, host)
+
+
 class KernelCheckError(RuntimeError):
     """An out-of-range device index caught by the checked kernel build."""
 

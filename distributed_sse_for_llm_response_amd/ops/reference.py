@@ -222,6 +222,18 @@ def kv_pages_scatter(staging, blocks, k_cache, v_cache):
         vb[:, idx] = sb[:n, 1].transpose(0, 1)
 
 
+def kv_pages_copy(k_cache, v_cache, pairs):
+    """Page pairs[i][1] = page pairs[i][0], every layer, K and V (bytes only: bf16 and fp8 caches alike).  The sources
+    are read before anything is written, as on the device, where no destination is a source."""
+    if pairs.numel() == 0:
+        return
+    L, nb = k_cache.shape[:2]
+    src, dst = pairs[:, 0].long(), pairs[:, 1].long()
+    for c in (k_cache, v_cache):
+        b = c.view(torch.uint8).view(L, nb, -1)
+        b[:, dst] = b[:, src].clone()
+
+
 # ---------------------------------------------------------------- attention
 def gather_kv(k_cache, v_cache, block_table, n, k_scale=1.0, v_scale=1.0):
     """Keys/values 0..n-1 of one sequence in natural order: ([n, Hkv, 128], [n, Hkv, 128]); an fp8 cache is

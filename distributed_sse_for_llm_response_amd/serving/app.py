@@ -126,6 +126,9 @@ class EngineLoop(threading.Thread):
         # host KV tier: its counters travel the same way, and /metrics names them only when the tier is on
         self._offload = getattr(getattr(engine, "engine", engine), "offload", None) is not None
         self._offload_seen = [0, 0, 0, 0]
+        # parallel sampling (n > 1): its counters travel the same way, and /metrics names them only once a request
+        # with n > 1 was seen (a server that never sees one shows what it always showed)
+        self._fork_seen = [0, 0, 0]
         if self._offload and not self._remote:
             rt.observe_kv_offload(0, 0, 0, 0)
         if self._prefix_cache and not self._remote:
@@ -172,11 +175,20 @@ class EngineLoop(threading.Thread):
             guide_schema=bool(req.get("guide_schema")),  # guided_json / response_format json_schema, lowered
             json_object=bool(req.get("guide_json")))  # response_format {"type": "json_object"}
 
+    @staticmethod
+    def choice_ids(req) -> list:
+        """The conversation ids of a request's choices (parallel sampling, n > 1): the id itself for choice 0, then
+        f"{id}-c{i}" -- the subjects the HTTP server subscribed to, and the ids the engine derives."""
+        conv = req["conversation_id"]
+        return [conv] + [f"{conv}-c{i}" for i in range(1, max(1, int(req.get("n", 1))))]
+
     def _watch_stop(self, req, prompt, params: SamplingParams) -> None:
-        """A request with stop strings: its events pass through the matcher from now on."""
+        """A request with stop strings: its events pass through the matcher from now on (every choice on its own: the
+        matcher's state is keyed by conversation id)."""
         if self.stops is not None and params is not None and params.stop:
             n = min(len(prompt), self.engine.r.max_model_len - 1)  # (what the engine keeps of the prompt)
-            self.stops.register(req["conversation_id"], params.stop, min(params.min_tokens, params.max_tokens), n)
+            for conv in self.choice_ids(req):
+                self.stops.register(conv, params.stop, min(params.min_tokens, params.max_tokens), n)
 
     def stop_aborts(self) -> list:
         """Conversations a stop string ended since the last call: the loop aborts them in the engine."""
@@ -243,8 +255,8 @@ class EngineLoop(threading.Thread):
             return prompt_for_request(self.tok, req)
         except Exception as e:  # noqa: BLE001 - any tokenizer / template failure is this request's error
             self.tokenize_errors += 1
-            self.publish([TokenEvent(req["conversation_id"], -1, 1, True, text="[ERROR]", timestamp_ns=time.time_ns(),
-                                     finish="abort", prompt_tokens=0)])
+            self.publish([TokenEvent(conv, -1, 1, True, text="[ERROR]", timestamp_ns=time.time_ns(),
+                                     finish="abort", prompt_tokens=0) for conv in self.choice_ids(req)])
             print(f"[engine] request {req['conversation_id']} rejected by the tokenizer: {e!r}", flush=True)
             return None
 
@@ -254,7 +266,11 @@ class EngineLoop(threading.Thread):
             if prompt is not None:
                 params = self._params(req)
                 self._watch_stop(req, prompt, params)
-                self.engine.add_request(req["conversation_id"], prompt, params, arrival_ns=req["arrival_ns"])
+                n = int(req.get("n", 1))
+                if n > 1:  # the choices of one request: one prefill, forked KV pages (LLMEngine.add_request)
+                    self.engine.add_request(req["conversation_id"], prompt, params, arrival_ns=req["arrival_ns"], n=n)
+                else:
+                    self.engine.add_request(req["conversation_id"], prompt, params, arrival_ns=req["arrival_ns"])
 
     def _jit_wait(self):
         """Wait until the just-in-time deadline (LLMEngine.jit_delay), taking in the requests that arrive meanwhile
@@ -286,6 +302,9 @@ class EngineLoop(threading.Thread):
                 d = self._offload_delta()
                 if any(d):
                     self._rt.observe_kv_offload(*d)
+            d = self._fork_delta()
+            if any(d):
+                self._rt.observe_parallel_sampling(*d)
             return
         if host >= 0:
             self._host.append(host)
@@ -297,9 +316,12 @@ class EngineLoop(threading.Thread):
         self._ttft.clear()
         self._itl.clear()
         self._host.clear()
-        if self._prefix_cache:
-            self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs,
-                            self._prefix_delta() + (self._offload_delta() if self._offload else []))
+        prefix = self._prefix_delta() + (self._offload_delta() if self._offload else []) if self._prefix_cache else []
+        fork = self._fork_delta()
+        if any(fork):  # (a replica that has seen a request with n > 1: its counters ride behind the prefix cache's)
+            self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs, prefix, fork)
+        elif self._prefix_cache:
+            self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs, prefix)
         else:
             self.rt.observe(e.stats["last_step_s"], running, free, running + len(e.waiting), ttft, itl, hs)
 
@@ -309,6 +331,14 @@ class EngineLoop(threading.Thread):
         now = [st.get("prefix_queries", 0), st.get("prefix_hit_tokens", 0), st.get("prefix_evictions", 0)]
         d = [float(a - b) for a, b in zip(now, self._prefix_seen)]
         self._prefix_seen = now
+        return d
+
+    def _fork_delta(self) -> list:
+        """[requests with n > 1, prompt tokens their siblings did not prefill, tail pages copied] since the last call."""
+        st = self.engine.stats
+        now = [st.get("fork_requests", 0), st.get("fork_shared_tokens", 0), st.get("fork_tail_copies", 0)]
+        d = [float(a - b) for a, b in zip(now, self._fork_seen)]
+        self._fork_seen = now
         return d
 
     def _offload_delta(self) -> list:
@@ -338,8 +368,10 @@ class EngineLoop(threading.Thread):
                 # only paused streams left: wait briefly so their resume events get through
                 wait = 0 if busy else (2 if self.engine.has_work() else 20)
                 self._take(self.rt.poll_requests(256, wait))
-                for conv in list(self.rt.pop_cancellations()) + self.stop_aborts():
+                for conv in self.rt.pop_cancellations():
                     self.engine.abort(conv)
+                for conv in self.stop_aborts():  # a stop string ends the choice it matched in, not its siblings
+                    self.engine.abort(conv, choices=False)
                 for conv, paused in self.flow_events():
                     self.engine.set_paused(conv, paused)
                 if not self.engine.runnable():

@@ -195,6 +195,10 @@ class ServeConfig:
                 "inspection_timeout_ms", "inspection_fail_open", "dedupe_window_s", "model_name", "keepalive_ms",
                 "first_token_timeout_ms", "flow_high_water")
         out = {k: d[k] for k in keys}
+        # `n` of POST /v1/chat/completions: at most 16 choices, and no more than the engine has decode slots (the CPU
+        # engine is built with min(MAX_BATCH, 8): serving/app.py build_engine)
+        slots = min(self.max_batch, 8) if self.engine == "cpu" else self.max_batch
+        out["max_choices"] = max(1, min(16, int(slots)))
         if self.ui_path != "none":
             from pathlib import Path
 

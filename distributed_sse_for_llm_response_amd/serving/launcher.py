@@ -52,9 +52,12 @@ class TPLeaderLoop(EngineLoop):
                     if prompt is not None:
                         params = self._params(req)
                         self._watch_stop(req, prompt, params)  # (stop strings stay here: only the leader has text)
-                        self.drv.add(req["conversation_id"], prompt, params, req["arrival_ns"])
-                for conv in list(self.rt.pop_cancellations()) + self.stop_aborts():
+                        self.drv.add(req["conversation_id"], prompt, params, req["arrival_ns"],
+                                     n=max(1, int(req.get("n", 1))))
+                for conv in self.rt.pop_cancellations():
                     self.drv.abort(conv)
+                for conv in self.stop_aborts():  # a stop string ends the choice it matched in, not its siblings
+                    self.drv.abort(conv, choices=False)
                 for conv, paused in self.flow_events():  # pause timeouts are decided here, so all ranks agree
                     self.drv.set_paused(conv, paused)
                 run = bool(self.drv.plan.adds) or self.engine.runnable()

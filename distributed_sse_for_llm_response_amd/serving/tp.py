@@ -48,8 +48,10 @@ class Plan:
     step: bool = False
     stop: bool = False
     sync: bool = False  # followers run the caller's sync hook after the step (e.g. a timing barrier)
-    adds: list = field(default_factory=list)    # (rid, prompt ids, SamplingParams, arrival_ns)
-    aborts: list = field(default_factory=list)  # rid
+    # (rid, prompt ids, SamplingParams, arrival_ns), or with a fifth element n > 1: the n choices of one request,
+    # rids rid .. rid + n - 1 (parallel sampling; n - 1 rides in bits 3..7 of the flag word, so n = 1 encodes as ever)
+    adds: list = field(default_factory=list)
+    aborts: list = field(default_factory=list)  # rid (a request with n > 1: all its choices), or -rid: that one only
     flow: list = field(default_factory=list)    # (rid, paused)
 
     def empty(self) -> bool:
@@ -58,7 +60,11 @@ class Plan:
     # ---- int32 wire form ----------------------------------------------------------------------
     def encode(self) -> list:
         w = []
-        for rid, prompt, p, arrival in self.adds:
+        for add in self.adds:
+            rid, prompt, p, arrival = add[:4]
+            n_choices = int(add[4]) if len(add) > 4 else 1
+            if not 1 <= n_choices <= 32:
+                raise ValueError(f"TP plan: n = {n_choices} outside [1, 32]")
             # seeds travel whole: two 31-bit words (the server accepts seeds up to 2^53 - 1); -1 = no seed
             if p.seed is None:
                 s_lo, s_hi = -1, -1
@@ -69,7 +75,8 @@ class Plan:
                 s_lo, s_hi = sd & 0x7FFFFFFF, (sd >> 31) & 0x7FFFFFFF
             w += [rid, arrival & 0x7FFFFFFF, (arrival >> 31) & 0x7FFFFFFF, int(p.max_tokens), int(p.top_k), s_lo, s_hi,
                   # (bit 1: JSON mode; bit 2: the guide is schema-derived)
-                  int(bool(p.ignore_eos)) | (2 if p.json_object else 0) | (4 if p.guide_schema else 0),
+                  int(bool(p.ignore_eos)) | (2 if p.json_object else 0) | (4 if p.guide_schema else 0)
+                  | ((n_choices - 1) << 3),
                   _f2i(p.temperature), _f2i(p.top_p), _f2i(p.presence_penalty), _f2i(p.frequency_penalty), _f2i(p.repetition_penalty), int(p.logprobs), int(p.min_tokens),
                   _f2i(p.min_p), len(p.logit_bias or ()), len(p.stop_token_ids), len(prompt)]
             guide = None if p.guide is None else p.guide.encode("utf-8")
@@ -114,7 +121,9 @@ class Plan:
                                 repetition_penalty=_i2f(rep), logprobs=lp, logit_bias=bias or None, min_tokens=mn,
                                 stop_token_ids=stop_ids, min_p=_i2f(min_p), guide=guide, json_object=bool(ie & 2),
                                 guide_schema=bool(ie & 4))
-            p.adds.append((rid, prompt, sp, a_lo | (a_hi << 31)))
+            n_choices = ((ie >> 3) & 31) + 1
+            add = (rid, prompt, sp, a_lo | (a_hi << 31))
+            p.adds.append(add if n_choices == 1 else add + (n_choices,))
         for _ in range(n_abort):
             p.aborts.append(w[o])
             o += 1
@@ -281,10 +290,18 @@ def follower_conv(rid: int) -> str:
 
 def apply_plan(engine, plan: Plan, conv_of=follower_conv) -> None:
     """Apply a plan's admissions, aborts and flow changes to an engine, in that order (leader and followers)."""
-    for rid, prompt, params, arrival in plan.adds:
-        engine.add_request(conv_of(rid), prompt, params, arrival_ns=arrival, rid=rid)
+    for add in plan.adds:
+        rid, prompt, params, arrival = add[:4]
+        if len(add) > 4 and add[4] > 1:  # the choices of one request: every rank makes the same n sequences
+            engine.add_request(conv_of(rid), prompt, params, arrival_ns=arrival, rid=rid, n=add[4],
+                               choice_ids=[conv_of(rid + i) for i in range(add[4])])
+        else:
+            engine.add_request(conv_of(rid), prompt, params, arrival_ns=arrival, rid=rid)
     for rid in plan.aborts:
-        engine.abort(conv_of(rid))
+        if rid < 0:
+            engine.abort(conv_of(-rid), choices=False)
+        else:
+            engine.abort(conv_of(rid))
     for rid, paused in plan.flow:
         engine.set_paused(conv_of(rid), paused)
 
@@ -298,15 +315,22 @@ class TPLeader:
         self._conv = {}   # rid -> conversation id (leader's real ids)
         self._rid = {}    # conversation id -> rid
 
-    def add(self, conversation_id: str, prompt: list, params: SamplingParams, arrival_ns: int) -> None:
+    def add(self, conversation_id: str, prompt: list, params: SamplingParams, arrival_ns: int, n: int = 1) -> None:
         rid = self.engine.next_rid()
         self._conv[rid], self._rid[conversation_id] = conversation_id, rid
-        self.plan.adds.append((rid, list(prompt), params, arrival_ns))
+        if n == 1:
+            self.plan.adds.append((rid, list(prompt), params, arrival_ns))
+            return
+        for i in range(1, n):  # choice i: the next rid, under the derived conversation id
+            r_i, cid = self.engine.next_rid(), f"{conversation_id}-c{i}"
+            assert r_i == rid + i, "parallel sampling: rids must be consecutive"
+            self._conv[r_i], self._rid[cid] = cid, r_i
+        self.plan.adds.append((rid, list(prompt), params, arrival_ns, n))
 
-    def abort(self, conversation_id: str) -> None:
+    def abort(self, conversation_id: str, choices: bool = True) -> None:
         rid = self._rid.get(conversation_id)
         if rid is not None:
-            self.plan.aborts.append(rid)
+            self.plan.aborts.append(rid if choices else -rid)
 
     def set_paused(self, conversation_id: str, paused: bool) -> None:
         rid = self._rid.get(conversation_id)
