@@ -15,6 +15,14 @@ enum GemmMode { kStoreBf16 = 0, kStoreF32 = 1, kResidAdd = 2, kSiluMul = 3, kQkv
 // therefore loads every block as four fully contiguous 1 KiB runs (see ops/reference.py tile_weight).
 constexpr int kTileChunk = 16 * 128;  // elements per (tile, chunk) block
 
+// FP8 weights (gemm_w8.hip; ops/reference.py quantize_weight_f8 / tile_weight_f8): Wq[N, K] holds one e4m3fn byte per
+// element, value = bf16(byte) * scale[row] with one fp32 power-of-two scale per row.  Byte form of the tiled layout:
+// the same (16-row tile T, 128-column K-chunk c) blocks, block-major (T, c), 2 KiB each; inside a block
+// [h = 0..1][lane = 0..63][b = 0..15] where lane l = r + 16g holds Wq[16T + r][128c + 32g + 16h + b] -- 16 contiguous
+// bytes per lane: bytes 0-7 widen to the MFMA B-operand fragment of k-step 2h, bytes 8-15 to that of k-step 2h + 1
+// (the same k = 32g + 8s + j as the bf16 layout).  A wave loads every block as two fully contiguous 1 KiB runs.
+constexpr int kTileChunkF8 = 16 * 128;  // bytes per (tile, chunk) block
+
 struct GemmEpi {
   void* out;          // bf16 / f32 output (modes 0, 1, 3)
   int ldo;
@@ -234,6 +242,8 @@ hipError_t dsse_gemm_stream(int mode, int mt, int nt, int nw, int rd, int S, int
                             const void* W, int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
 hipError_t dsse_gemm_ring(int mode, int nw, int S, int partial_only, int ring2, const void* X, int ldx, int M,
                           const void* W, int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
+hipError_t dsse_gemm_w8(int mode, int nw, int S, int partial_only, const void* X, int ldx, int M, const void* W,
+                        const float* scale, int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
 hipError_t dsse_gemm_wide(int mode, int mb, int rd, int S, int partial_only, const void* X, int ldx, int M, const void* W,
                           int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
 hipError_t dsse_gemm_tiled(int mode, int cfg, int S, int partial_only, const void* X, int ldx, int M, const void* W,
@@ -305,6 +315,7 @@ hipError_t dsse_check_elementwise(int* out, int clear);
 hipError_t dsse_check_sampler(int* out, int clear);
 hipError_t dsse_check_gemm_tiled(int* out, int clear);
 hipError_t dsse_check_kv_pages(int* out, int clear);
+hipError_t dsse_check_gemm_w8(int* out, int clear);
 // Stamps build: bind the step-anatomy record buffer (common.h stamps::) of a kernel file; no-ops otherwise.
 hipError_t dsse_stamps_bind_gemm_stream(void* rec);
 hipError_t dsse_stamps_bind_elementwise(void* rec);

@@ -108,6 +108,8 @@ def _build_runner(model: str, device, streams: int, prompt_len: int, total_steps
     # benchmark times an fp8 cache without a flag of its own
     if kv_cache_dtype is None:
         kv_cache_dtype = os.environ.get("KV_CACHE_DTYPE") or "auto"
+    # likewise the serving key QUANTIZATION (none | fp8): unset, the weights and every kernel are what they were
+    quantization = os.environ.get("QUANTIZATION") or None
     # on CPU the 7B architecture is replaced by the tiny one (plumbing runs); named small configs are kept
     cfg = get_config(model) if device.type == "cuda" or not model.startswith("mistral-7b") else TINY
     if comm is None:
@@ -117,7 +119,8 @@ def _build_runner(model: str, device, streams: int, prompt_len: int, total_steps
 
             grp, _ = make_groups(world, tp)
             comm = TPComm(rank=rank % tp, size=tp, group=grp)
-    w = random_engine_weights(cfg, tp_rank=comm.rank, tp_size=comm.size, device=device, seed=1234)
+    w = random_engine_weights(cfg, tp_rank=comm.rank, tp_size=comm.size, device=device, seed=1234,
+                              **({"quantization": quantization} if quantization else {}))
     max_len = prompt_len + total_steps + 2 * PAGE
     nblk = streams * (blocks_needed(max_len) + 1) + 4
     runner = ModelRunner(w, num_blocks=nblk, max_batch=streams, max_model_len=max_len, device=device, comm=comm,

@@ -39,7 +39,7 @@ from .. import ops
 from ..ops.reference import rope_table
 from ..parallel.comm import TPComm
 from .kv_cache import PAGE, KVCache
-from .weights import EngineWeights
+from .weights import EngineWeights, parse_quantization, quantize_engine_weights
 
 RING_SIZE = 64
 SAMPLE_CHUNKS = 16  # vocab chunks per row in the candidate pass (B x 16 workgroups)
@@ -209,7 +209,17 @@ class SampleSite(NamedTuple):
 class ModelRunner:
     def __init__(self, w: EngineWeights, num_blocks: int, max_batch: int = 64, max_model_len: int = 4096,
                  max_prefill_tokens: int = 8192, device="cuda", comm: TPComm | None = None, use_graphs=None,
-                 kv_cache_dtype="auto"):
+                 kv_cache_dtype="auto", quantization=None):
+        # quantization "fp8": FP8 (e4m3) weights beside a widened bf16 copy (engine/weights.py).  Decode buckets of
+        # W8_MAX_M rows or fewer run every projection and the LM head on the FP8 kernels over *_q; wider buckets,
+        # prefill, mixed steps and the first-token head use the existing kernels over the widened *_t -- identical
+        # weight values on both paths.  None = as the weights were loaded.
+        if quantization is not None and parse_quantization(quantization) != "none":
+            if (comm.size if comm is not None else 1) > 1:
+                raise ValueError("quantization=fp8 is not supported with tensor parallelism (tp > 1)")
+            quantize_engine_weights(w, quantization)
+        self.quantization = "fp8_e4m3" if w.quantization == "fp8" else "none"
+        self.w8 = w.quantization == "fp8"
         self.w, self.cfg = w, w.cfg
         self.device = torch.device(device)
         self.comm = comm or TPComm()
@@ -362,6 +372,17 @@ class ModelRunner:
         if B > DECODE_GEMM_MAX_M:
             self._decode_layers_wide(B, resid, x, part, nparts)
             return
+        if self.w8 and B <= ops.W8_MAX_M:
+            for li, L in enumerate(w.layers):
+                self._qkv_attention(li, L, B, x, part, nparts)
+                self._resid_proj_w8(self.attn[r], L.wo_q, L.wo_scale, resid, L.ffn_norm, x)
+                ops.gemm_silu_w8(x, L.wgu_q, L.wgu_scale, self.h[r])
+                w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
+                self._resid_proj_w8(self.h[r], L.wd_q, L.wd_scale, resid, w_next, x)
+            ops.gemm_out_w8(x, w.lm_head_q, w.lm_head_scale, self.logits[r])
+            self._sample_commit(B)
+            ops.ring_advance(self.ring_counter)
+            return
         for li, L in enumerate(w.layers):
             self._qkv_attention(li, L, B, x, part, nparts)
             self._resid_proj(self.attn[r], L.wo_t, resid, L.ffn_norm, x, self.tmp[r])
@@ -405,6 +426,13 @@ class ModelRunner:
         RoPE and the K/V write in (ops.qkv_attention_decode)."""
         r = slice(0, B)
         nh, nkv = self.w.nh, self.w.nkv
+        if self.w8 and B <= ops.W8_MAX_M:
+            ops.qkv_attention_decode_w8(x, L.wqkv_q, L.wqkv_scale, self.positions[r], self.slots[r], self.rope,
+                                        self.q[r], self.kv.k[li], self.kv.v[li], nh, nkv, self.split_part,
+                                        self.block_tables[r], self.q_start[r], self.q_len[r], self.ctx_len[r],
+                                        self.work_seq[r], self.work_tile[r], self.attn[r], self.part_o, self.part_ml,
+                                        part, nparts, *self._kv_scales(li))
+            return
         ops.qkv_attention_decode(x, L.wqkv_t, self.positions[r], self.slots[r], self.rope, self.q[r], self.kv.k[li],
                                  self.kv.v[li], nh, nkv, self.split_part, self.block_tables[r], self.q_start[r],
                                  self.q_len[r], self.ctx_len[r], self.work_seq[r], self.work_tile[r], self.attn[r],
@@ -442,6 +470,11 @@ class ModelRunner:
         else:
             ops.gemm_out(a, wt, tmp)
             self.comm.all_reduce_rmsnorm(tmp, resid, norm_w, x, eps)
+
+    def _resid_proj_w8(self, a, wq, ws, resid, norm_w, x) -> None:
+        """_resid_proj over an FP8 weight (TP = 1): the scaled split-K slabs are reduced inside the norm."""
+        ns = ops.gemm_resid_split_w8(a, wq, ws, resid, self.split_part)
+        ops.rmsnorm(resid, norm_w, x, self.cfg.rms_eps, part=self.split_part, nsplit=ns)
 
     def _sample_commit(self, B: int) -> None:
         """The decode step's sampling (decode and mixed graphs): row b is slot b, the pick commits ids / ring row /

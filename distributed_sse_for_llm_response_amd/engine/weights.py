@@ -18,6 +18,11 @@ every weight load instruction reads 1 KiB of contiguous HBM, and a (16-column, 3
 fragment.  The row-major [out, in] matrices above are only the conversion input; :func:`attach_tiled` drops
 them, so the model is resident once (round 1 kept both layouts for the library prefill GEMMs: 14.5 GB more for
 Mistral-7B at TP=1, now KV cache).
+
+``quantization="fp8"`` (TP = 1 only) quantises the five matrices once, at load, in the engine layout (so the scale
+index is the engine row): ``*_q`` = e4m3 bytes in the byte tiled layout (:func:`ops.reference.tile_weight_f8`),
+``*_scale`` = one fp32 power-of-two scale per row, and ``*_t`` = the tiled copy of ``bf16(q) * scale`` (exact), which
+every kernel without an FP8 form keeps using.  Embedding, norms and rope are left alone.
 """
 from __future__ import annotations
 
@@ -27,7 +32,19 @@ from dataclasses import dataclass
 import torch
 
 from ..models.mistral import MistralConfig
-from ..ops.reference import gate_up_perm, rotary_perm, tile_weight
+from ..ops.reference import (gate_up_perm, quantize_weight_f8, rotary_perm, tile_weight, tile_weight_f8,
+                             untile_weight, widen_weight_f8)
+
+QUANTIZATIONS = ("none", "fp8")  # weight quantisation at load: none = bf16 only; fp8 = W8A16 e4m3 beside a widened copy
+
+
+def parse_quantization(v) -> str:
+    """None / "" / "none" -> "none"; "fp8" (or "fp8_e4m3") -> "fp8"; anything else is an error naming the choices."""
+    key = "none" if v is None else str(v).strip().lower()
+    key = {"": "none", "fp8_e4m3": "fp8"}.get(key, key)
+    if key not in QUANTIZATIONS:
+        raise ValueError(f"quantization / QUANTIZATION must be one of {', '.join(QUANTIZATIONS)}; got {v!r}")
+    return key
 
 
 @dataclass
@@ -43,6 +60,16 @@ class LayerWeights:
     wo_t: torch.Tensor = None
     wgu_t: torch.Tensor = None
     wd_t: torch.Tensor = None
+    # FP8 weights (quantization="fp8"): *_q = e4m3 bytes in the byte tiled layout (tile_weight_f8), *_scale = fp32
+    # power-of-two scale per engine row; *_t is then the widened copy tile_weight(bf16(q) * scale)
+    wqkv_q: torch.Tensor = None
+    wqkv_scale: torch.Tensor = None
+    wo_q: torch.Tensor = None
+    wo_scale: torch.Tensor = None
+    wgu_q: torch.Tensor = None
+    wgu_scale: torch.Tensor = None
+    wd_q: torch.Tensor = None
+    wd_scale: torch.Tensor = None
     # per-layer dequantisation scales of an fp8 KV cache (stored = x / scale); 1.0 unless the checkpoint carries
     # vLLM's model.layers.N.self_attn.k_scale / .v_scale.  The same on every TP rank.  Unused with a bf16 cache.
     k_scale: float = 1.0
@@ -59,6 +86,9 @@ class EngineWeights:
     final_norm: torch.Tensor
     lm_head: torch.Tensor
     lm_head_t: torch.Tensor = None
+    lm_head_q: torch.Tensor = None
+    lm_head_scale: torch.Tensor = None
+    quantization: str = "none"
 
     @property
     def nh(self) -> int:
@@ -81,24 +111,66 @@ class EngineWeights:
         return self.tp_rank * self.vocab_local
 
     def nbytes(self) -> int:
-        """Bytes of the resident model (what a decode step streams, plus the embedding table)."""
+        """Bytes of the resident model: the bf16 copy (what a decode step streams, plus the embedding table) and,
+        under quantization, the FP8 copy beside it."""
         n = self.embed.numel() + self.final_norm.numel() + self.lm_head_t.numel()
         for L in self.layers:
             n += sum(t.numel() for t in (L.attn_norm, L.wqkv_t, L.wo_t, L.ffn_norm, L.wgu_t, L.wd_t))
-        return 2 * n
+        return 2 * n + self.nbytes_fp8()
+
+    def nbytes_fp8(self) -> int:
+        """Bytes of the FP8 copy (bytes and scales of every quantised matrix); 0 without quantization."""
+        ts = [self.lm_head_q, self.lm_head_scale]
+        for L in self.layers:
+            ts += [L.wqkv_q, L.wqkv_scale, L.wo_q, L.wo_scale, L.wgu_q, L.wgu_scale, L.wd_q, L.wd_scale]
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+
+def _tile(m: torch.Tensor, quantization: str):
+    """(tiled bf16, tiled e4m3 bytes, scales) of one engine-layout matrix: quantised per engine row, the bf16 copy
+    widened from the bytes, so both copies hold identical values; (tile_weight(m), None, None) without quantization."""
+    if quantization != "fp8":
+        return tile_weight(m), None, None
+    q, scale = quantize_weight_f8(m)
+    return tile_weight(widen_weight_f8(q, scale).to(m.dtype)), tile_weight_f8(q), scale
+
+
+def _tile_layer(L: LayerWeights, quantization: str) -> None:
+    L.wqkv_t, L.wqkv_q, L.wqkv_scale = _tile(L.wqkv, quantization)
+    L.wo_t, L.wo_q, L.wo_scale = _tile(L.wo, quantization)
+    L.wgu_t, L.wgu_q, L.wgu_scale = _tile(L.wgu, quantization)
+    L.wd_t, L.wd_q, L.wd_scale = _tile(L.wd, quantization)
+    L.wqkv = L.wo = L.wgu = L.wd = None
 
 
 @torch.no_grad()
-def attach_tiled(w: EngineWeights) -> EngineWeights:
-    """Convert every GEMM weight to the tiled layout and drop the row-major input (idempotent)."""
+def attach_tiled(w: EngineWeights, quantization=None) -> EngineWeights:
+    """Convert every GEMM weight to the tiled layout and drop the row-major input (idempotent).  quantization="fp8":
+    the matrices (not the embedding, the norms or rope) are quantised here, once, in the engine layout."""
+    w.quantization = parse_quantization(quantization) if w.quantization == "none" else w.quantization
     for L in w.layers:
         if L.wqkv_t is None:
-            L.wqkv_t, L.wo_t = tile_weight(L.wqkv), tile_weight(L.wo)
-            L.wgu_t, L.wd_t = tile_weight(L.wgu), tile_weight(L.wd)
+            _tile_layer(L, w.quantization)
         L.wqkv = L.wo = L.wgu = L.wd = None
     if w.lm_head_t is None:
-        w.lm_head_t = tile_weight(w.lm_head)
+        w.lm_head_t, w.lm_head_q, w.lm_head_scale = _tile(w.lm_head, w.quantization)
     w.lm_head = None
+    return w
+
+
+@torch.no_grad()
+def quantize_engine_weights(w: EngineWeights, quantization="fp8") -> EngineWeights:
+    """Quantise engine weights that were loaded without the option (idempotent): each matrix is taken back from its
+    tiled bf16 copy, quantised per engine row, and both copies are stored as the loaders would have."""
+    q = _check_quantization(quantization, w.tp_size)
+    if q == "none" or w.quantization == q:
+        return w
+    attach_tiled(w)
+    for L in w.layers:
+        L.wqkv, L.wo, L.wgu, L.wd = (untile_weight(t) for t in (L.wqkv_t, L.wo_t, L.wgu_t, L.wd_t))
+        _tile_layer(L, q)
+    w.lm_head_t, w.lm_head_q, w.lm_head_scale = _tile(untile_weight(w.lm_head_t), q)
+    w.quantization = q
     return w
 
 
@@ -119,8 +191,18 @@ def _kv_scale(t) -> float:
     return v
 
 
-def convert_standard(cfg: MistralConfig, std, tp_rank: int = 0, tp_size: int = 1, device="cpu") -> EngineWeights:
-    """Standard (HF-layout) weights -> this rank's engine weights."""
+def _check_quantization(quantization, tp_size: int) -> str:
+    q = parse_quantization(quantization)
+    if q != "none" and tp_size > 1:
+        raise ValueError("quantization=fp8 is not supported with tensor parallelism (tp > 1): the row scales are not "
+                         "sharded; use --dp for more than one GPU")
+    return q
+
+
+def convert_standard(cfg: MistralConfig, std, tp_rank: int = 0, tp_size: int = 1, device="cpu",
+                     quantization=None) -> EngineWeights:
+    """Standard (HF-layout) weights -> this rank's engine weights (quantization="fp8": quantised once, here)."""
+    quantization = _check_quantization(quantization, tp_size)
     cfg.validate(tp_size)
     D = cfg.head_dim
     nh, nkv, F = cfg.num_heads // tp_size, cfg.num_kv_heads // tp_size, cfg.intermediate_size // tp_size
@@ -144,18 +226,20 @@ def convert_standard(cfg: MistralConfig, std, tp_rank: int = 0, tp_size: int = 1
             k_scale=_kv_scale(L.get("k_scale")), v_scale=_kv_scale(L.get("v_scale"))))
     return attach_tiled(EngineWeights(
         cfg=cfg, tp_rank=tp_rank, tp_size=tp_size, embed=std["embed"].contiguous().to(device), layers=layers,
-        final_norm=std["final_norm"].contiguous().to(device), lm_head=std["lm_head"][r * V:(r + 1) * V].contiguous().to(device)))
+        final_norm=std["final_norm"].contiguous().to(device), lm_head=std["lm_head"][r * V:(r + 1) * V].contiguous().to(device)),
+        quantization)
 
 
 @torch.no_grad()
 def random_engine_weights(cfg: MistralConfig, tp_rank: int = 0, tp_size: int = 1, device="cuda",
-                          seed: int = 0, dtype=torch.bfloat16) -> EngineWeights:
+                          seed: int = 0, dtype=torch.bfloat16, quantization=None) -> EngineWeights:
     """Random weights generated directly on the device in engine layout (the 7B bench path).
 
     Generating 14.5 GB through the standard layout on the host would take minutes; the engine layout
     is a fixed row permutation of the standard one, so the distribution is identical.  Each rank
     draws its own shard (seeded by (seed, rank)), i.e. the global model is a valid random model.
     """
+    quantization = _check_quantization(quantization, tp_size)
     cfg.validate(tp_size)
     D, H = cfg.head_dim, cfg.hidden_size
     nh, nkv, F = cfg.num_heads // tp_size, cfg.num_kv_heads // tp_size, cfg.intermediate_size // tp_size
@@ -179,14 +263,14 @@ def random_engine_weights(cfg: MistralConfig, tp_rank: int = 0, tp_size: int = 1
     for _ in range(cfg.num_layers):
         L = LayerWeights(attn_norm=norm(H), wqkv=lin((nh + 2 * nkv) * D, H), wo=lin(H, nh * D),
                          ffn_norm=norm(H), wgu=lin(2 * F, H), wd=lin(H, F))
-        L.wqkv_t, L.wo_t, L.wgu_t, L.wd_t = (tile_weight(t) for t in (L.wqkv, L.wo, L.wgu, L.wd))
-        L.wqkv = L.wo = L.wgu = L.wd = None  # one layer's row-major copy at a time
+        _tile_layer(L, quantization)  # one layer's row-major copy at a time
         layers.append(L)
     return attach_tiled(EngineWeights(cfg=cfg, tp_rank=tp_rank, tp_size=tp_size, embed=embed, layers=layers,
-                                      final_norm=norm(H), lm_head=lin(V, H)))
+                                      final_norm=norm(H), lm_head=lin(V, H)), quantization)
 
 
-def load_safetensors(cfg: MistralConfig, path: str, tp_rank: int = 0, tp_size: int = 1, device="cpu") -> EngineWeights:
+def load_safetensors(cfg: MistralConfig, path: str, tp_rank: int = 0, tp_size: int = 1, device="cpu",
+                     quantization=None) -> EngineWeights:
     """Load an HF Mistral checkpoint directory (``*.safetensors``) into the engine layout."""
     from pathlib import Path
 
@@ -208,4 +292,4 @@ def load_safetensors(cfg: MistralConfig, path: str, tp_rank: int = 0, tp_size: i
             "down": tensors[p + "mlp.down_proj.weight"],
             "k_scale": tensors.get(p + "self_attn.k_scale"), "v_scale": tensors.get(p + "self_attn.v_scale"),
         })
-    return convert_standard(cfg, std, tp_rank, tp_size, device)
+    return convert_standard(cfg, std, tp_rank, tp_size, device, quantization)

@@ -115,6 +115,82 @@ def gemm_out_split(x, w, out, part) -> int:
     return 0
 
 
+# ---- FP8 weights (W8A16; csrc/kernels/gemm_w8.hip): w_q = e4m3 bytes in the byte tiled layout (reference.py
+# tile_weight_f8), w_scale = fp32 power-of-two row scales.  1-64 rows on the GPU; each op mirrors the bf16 op of the
+# same name and equals it on the widened weight tile_weight(widen_weight_f8(...)) up to fp32 summation order.
+W8_MAX_M = 64
+quantize_weight_f8, widen_weight_f8 = ref.quantize_weight_f8, ref.widen_weight_f8
+tile_weight_f8, untile_weight_f8 = ref.tile_weight_f8, ref.untile_weight_f8
+
+
+def gemm_out_w8(x, w_q, w_scale, out):
+    """out[M, N] = (x · w_qᵀ) * w_scale (bf16 or fp32 out)."""
+    if _hip(x):
+        torch.ops.dsse.gemm_out_w8(x, w_q, w_scale, out)
+    else:
+        ref.gemm_out_w8(x, w_q, w_scale, out)
+
+
+def gemm_resid_w8(x, w_q, w_scale, resid):
+    """resid[M, N] (fp32) += (x · w_qᵀ) * w_scale."""
+    if _hip(x):
+        torch.ops.dsse.gemm_resid_w8(x, w_q, w_scale, resid)
+    else:
+        ref.gemm_resid_w8(x, w_q, w_scale, resid)
+
+
+def gemm_silu_w8(x, w_q, w_scale, out):
+    """gemm_silu over an FP8 weight (interleaved gate/up rows)."""
+    if _hip(x):
+        torch.ops.dsse.gemm_silu_w8(x, w_q, w_scale, out)
+    else:
+        ref.gemm_silu_w8(x, w_q, w_scale, out)
+
+
+def gemm_resid_split_w8(x, w_q, w_scale, resid, part) -> int:
+    """gemm_resid_split over an FP8 weight: scaled fp32 slabs [S, M, N] in `part` and S, or the sum in resid and 0."""
+    if _hip(x):
+        return int(torch.ops.dsse.gemm_resid_split_w8(x, w_q, w_scale, resid, part))
+    ref.gemm_resid_w8(x, w_q, w_scale, resid)
+    return 0
+
+
+def gemm_out_split_w8(x, w_q, w_scale, out, part) -> int:
+    """gemm_out_split over an FP8 weight."""
+    if _hip(x):
+        return int(torch.ops.dsse.gemm_out_split_w8(x, w_q, w_scale, out, part))
+    ref.gemm_out_w8(x, w_q, w_scale, out)
+    return 0
+
+
+def gemm_qkv_rope_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0,
+                     v_scale=1.0, scratch=None):
+    """gemm_qkv_rope over an FP8 weight (the unfused path of qkv_attention_decode_w8)."""
+    if _hip(x):
+        torch.ops.dsse.gemm_qkv_rope_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv,
+                                        k_scale, v_scale, scratch)
+    else:
+        ref.gemm_qkv_rope_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale,
+                             v_scale)
+
+
+def qkv_attention_decode_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, slabs,
+                            block_tables, q_start, q_len, ctx_len, work_seq, work_tile, out, part_o, part_ml, part,
+                            nparts, k_scale=1.0, v_scale=1.0) -> int:
+    """qkv_attention_decode over an FP8 weight: the projection leaves scaled fp32 slabs that the attention kernel
+    folds in unchanged (returns the slab count; 0 = gemm_qkv_rope_w8 + paged_attention ran instead)."""
+    if _hip(x):
+        return int(torch.ops.dsse.qkv_attention_decode_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_cache,
+                                                          v_cache, nh, nkv, slabs, block_tables, q_start, q_len,
+                                                          ctx_len, work_seq, work_tile, out, part_o, part_ml, part,
+                                                          nparts, k_scale, v_scale))
+    B = x.shape[0]
+    ref.gemm_qkv_rope_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
+    ref.paged_attention(0, q_out.view(B, nh, 128), k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq,
+                        work_tile, out.view(B, nh, 128), part_o, part_ml, part, nparts, k_scale, v_scale)
+    return 0
+
+
 def kernel_cfg_env(**overrides) -> str:
     """The DSSE_KERNEL_CFG string (the kernel library's one configuration override: "key=value,..."; keys in
     csrc/kernels/bindings.cpp env_int, e.g. gemm_impl, t_cfg, s_nw) with `overrides` merged into the current value.

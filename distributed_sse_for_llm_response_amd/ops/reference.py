@@ -150,6 +150,71 @@ def gemm_qkv_rope(x, w, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv
     _write_kv(rot[:, nh:], qkv[:, nh + nkv:], slots[:M], k_cache, v_cache, k_scale, v_scale)
 
 
+# ---- FP8 (e4m3fn) weights, W8A16: the one definition of what a weight byte holds ---------------------------------
+# value = bf16(byte) * scale[row].  One fp32 scale per output row, a power of two: the smallest 2^e with
+# absmax(row) / 2^e <= 448 (a zero row: 1), so dividing by it is exact, the quotient never saturates, and the ONE
+# rounding is torch's round-to-nearest-even cast to e4m3fn (v_cvt_pk_fp8_f32's).  Every e4m3 value is exact in bf16 and
+# a power of two only moves the exponent, so widen_weight_f8 is exact in bf16 too: the FP8 kernels (bytes widened in
+# registers, accumulator times scale) and the bf16 kernels over the widened copy multiply by identical weight values.
+def quantize_weight_f8(w: torch.Tensor):
+    """w [N, K] -> (q float8_e4m3fn [N, K] row-major, scale fp32 [N])."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    _, e = torch.frexp(amax / FP8_MAX)  # amax / 448 ~ m 2^e with m in [0.5, 1): 2^e is the scale unless m == 0.5
+    s = torch.ldexp(torch.ones_like(amax), e)
+    # settle the candidate against amax itself (the quotient above is rounded); products with 2^e are exact
+    s = torch.where(FP8_MAX * (s * 0.5) >= amax, s * 0.5, s)
+    s = torch.where(FP8_MAX * s < amax, s * 2.0, s)
+    scale = torch.where(amax > 0, s, torch.ones_like(amax))
+    return (wf / scale[:, None]).to(FP8), scale
+
+
+def widen_weight_f8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The bf16 weight the FP8 bytes stand for (exact): bf16(q) * scale, row-major [N, K]."""
+    return (q.view(FP8).float() * scale.float()[:, None]).to(torch.bfloat16)
+
+
+def tile_weight_f8(q: torch.Tensor) -> torch.Tensor:
+    """Row-major [N, K] e4m3 bytes -> the byte form of the tiled layout (same shape and dtype, permuted storage).
+
+    The same (16-row tile T, 128-column chunk c) blocks as tile_weight, block-major (T, c), 2 KiB each; inside a block
+    byte [h][lane][b] with lane = r + 16 g holds Wq[16T + r][128c + 32g + 16h + b]: a lane's 16 bytes are contiguous
+    and widen to its MFMA B fragments of k-steps 2h and 2h + 1 (csrc/kernels/api.h kTileChunkF8).
+    """
+    N, K = q.shape
+    assert N % 16 == 0 and K % 128 == 0, (N, K)
+    b = q.view(torch.uint8).reshape(N // 16, 16, K // 128, 4, 2, 16).permute(0, 2, 4, 3, 1, 5).contiguous()
+    return b.view(N, K).view(q.dtype)
+
+
+def untile_weight_f8(qt: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`tile_weight_f8`."""
+    N, K = qt.shape
+    b = qt.view(torch.uint8).reshape(N // 16, K // 128, 2, 4, 16, 16).permute(0, 4, 1, 3, 2, 5).reshape(N, K)
+    return b.contiguous().view(qt.dtype)
+
+
+def _widened_tiled(wq, ws):
+    """The tiled bf16 weight of tiled FP8 bytes + scales: what the bf16 reference GEMMs take."""
+    return tile_weight(widen_weight_f8(untile_weight_f8(wq), ws))
+
+
+def gemm_out_w8(x, wq, ws, out):
+    gemm_out(x, _widened_tiled(wq, ws), out)
+
+
+def gemm_resid_w8(x, wq, ws, resid):
+    gemm_resid(x, _widened_tiled(wq, ws), resid)
+
+
+def gemm_silu_w8(x, wq, ws, out):
+    gemm_silu(x, _widened_tiled(wq, ws), out)
+
+
+def gemm_qkv_rope_w8(x, wq, ws, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
+    gemm_qkv_rope(x, _widened_tiled(wq, ws), positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
+
+
 def rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
     T = qkv.shape[0]
     u = _unpermute_units(qkv.float(), nh + 2 * nkv)

@@ -35,10 +35,13 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
     """Weights + KV cache + runner + engine for this process (one DP replica / TP rank)."""
     from ..engine.weights import convert_standard, load_safetensors, random_engine_weights
 
+    cfg.validate()  # option combinations (quantization with tp > 1, ...) fail here, before any weight is loaded
+    quant = cfg.quantization
     if cfg.engine == "cpu":
         mcfg = TINY if cfg.model.startswith("mistral-7b") else get_config(cfg.model)
         tp_rank, tp = (comm.rank, comm.size) if comm is not None else (0, 1)
-        w = convert_standard(mcfg, init_standard_weights(mcfg, seed=cfg.seed), tp_rank=tp_rank, tp_size=tp)
+        w = convert_standard(mcfg, init_standard_weights(mcfg, seed=cfg.seed), tp_rank=tp_rank, tp_size=tp,
+                             quantization=quant)
         runner = ModelRunner(w, num_blocks=256, max_batch=min(cfg.max_batch, 8),
                              max_model_len=min(cfg.max_model_len, 1024), device="cpu", comm=comm, use_graphs=False,
                              kv_cache_dtype=cfg.kv_cache_dtype)
@@ -47,9 +50,12 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         mcfg = get_config(cfg.model)
         tp_rank, tp = (comm.rank, comm.size) if comm is not None else (0, 1)
         if cfg.weights_path:
-            w = load_safetensors(mcfg, cfg.weights_path, tp_rank, tp, device)
+            w = load_safetensors(mcfg, cfg.weights_path, tp_rank, tp, device, quantization=quant)
         else:
-            w = random_engine_weights(mcfg, tp_rank=tp_rank, tp_size=tp, device=device, seed=cfg.seed)
+            w = random_engine_weights(mcfg, tp_rank=tp_rank, tp_size=tp, device=device, seed=cfg.seed,
+                                      quantization=quant)
+        # the page budget below is what is free once the weights are resident: under quantization both copies (the
+        # widened bf16 one, 14.5 GB for Mistral-7B, and the FP8 one, 7.2 GB) are already allocated here
         free, total = torch.cuda.mem_get_info(device)
         budget = int(total * cfg.gpu_memory_utilization) - (total - free) - (2 << 30)
         nkv = mcfg.num_kv_heads // tp
@@ -60,6 +66,10 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         runner.capture()
     kv = runner.kv
     if comm is None or comm.rank == 0:
+        f8 = w.nbytes_fp8()
+        print(f"[engine] weights: quantization {runner.quantization}, bf16 copy {(w.nbytes() - f8) / 1e9:.2f} GB"
+              + (f" (widened from fp8), fp8 copy {f8 / 1e9:.2f} GB (decode buckets of 64 rows or fewer)"
+                 if f8 else ""), flush=True)
         print(f"[engine] KV cache: {'fp8_e4m3' if kv.is_fp8 else 'bf16'} ({cfg.kv_cache_dtype}), "
               f"{KVCache.bytes_per_block(kv.num_layers, kv.nkv, kv.dtype) // 32 // 1024} KiB per token"
               f"{' per rank' if comm is not None and comm.size > 1 else ''}, {kv.num_blocks} pages of 32 tokens",

@@ -11,7 +11,8 @@ Flow control (new): FLOW_HIGH_WATER (bytes queued for every subscriber of a conv
 Engine keys (new): TP, DP, DP_PREFIX, DP_WORKER_TIMEOUT_MS, MAX_MODEL_LEN, MAX_BATCH, KV_BLOCK (fixed 32), GPU_MEMORY_UTILIZATION,
   SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH, ENABLE_PREFIX_CACHING (default 0),
   DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured), KV_CACHE_DTYPE (auto | bf16 | fp8 | fp8_e4m3; default auto = bf16),
-  KV_OFFLOAD_GB (GiB of pinned host memory per engine process behind the prefix cache; default 0 = off).
+  KV_OFFLOAD_GB (GiB of pinned host memory per engine process behind the prefix cache; default 0 = off),
+  QUANTIZATION (none | fp8; default none; fp8 = FP8 e4m3 weights for decode buckets of 64 rows or fewer, TP = 1).
 """
 from __future__ import annotations
 
@@ -29,6 +30,18 @@ def parse_kv_cache_dtype(v) -> str:
     key = str(v).strip().lower()
     if key not in KV_CACHE_DTYPES:
         raise ValueError(f"kv_cache_dtype / KV_CACHE_DTYPE must be one of {', '.join(KV_CACHE_DTYPES)}; got {v!r}")
+    return key
+
+
+# weight quantisation at load (engine/weights.py keeps its own copy of the list: no torch import at parse time)
+QUANTIZATIONS = ("none", "fp8")
+
+
+def parse_quantization(v) -> str:
+    """The option as typed (lower-cased); a value outside the choices is a start-up error that names them."""
+    key = str(v).strip().lower()
+    if key not in QUANTIZATIONS:
+        raise ValueError(f"quantization / QUANTIZATION must be one of {', '.join(QUANTIZATIONS)}; got {v!r}")
     return key
 
 
@@ -94,6 +107,9 @@ class ServeConfig:
     # host tier of the prefix cache: GiB of pinned host memory per engine process that keep evicted KV pages (0 = off;
     # needs enable_prefix_caching, not available with tp > 1); passed to every engine replica
     kv_offload_gb: float = 0.0
+    # weight quantisation at load: none, or fp8 = W8A16 e4m3 weights for decode buckets of 64 rows or fewer beside a
+    # widened bf16 copy for everything else (not available with tp > 1); passed to every engine replica
+    quantization: str = "none"
 
     @classmethod
     def from_env(cls) -> "ServeConfig":
@@ -140,6 +156,7 @@ class ServeConfig:
         c.dp_prefix_affinity_slack = _env("DP_PREFIX_AFFINITY_SLACK", c.dp_prefix_affinity_slack, int)
         c.kv_cache_dtype = _env("KV_CACHE_DTYPE", c.kv_cache_dtype, parse_kv_cache_dtype)
         c.kv_offload_gb = _env("KV_OFFLOAD_GB", c.kv_offload_gb, float)
+        c.quantization = _env("QUANTIZATION", c.quantization, parse_quantization)
         return c
 
     @classmethod
@@ -151,6 +168,9 @@ class ServeConfig:
             if f.name == "kv_cache_dtype":  # --help lists the choices; a bad value is a usage error that names them
                 ap.add_argument("--kv-cache-dtype", type=str.lower, choices=KV_CACHE_DTYPES, default=None)
                 continue
+            if f.name == "quantization":
+                ap.add_argument("--quantization", type=str.lower, choices=QUANTIZATIONS, default=None)
+                continue
             ap.add_argument("--" + f.name.replace("_", "-"), type=type(f.default) if f.default is not None else str,
                             default=None)
 
@@ -160,6 +180,7 @@ class ServeConfig:
             if v is not None:
                 setattr(self, f.name, v)
         self.kv_cache_dtype = parse_kv_cache_dtype(self.kv_cache_dtype)
+        self.quantization = parse_quantization(self.quantization)
         return self.validate()
 
     def validate(self) -> "ServeConfig":
@@ -175,6 +196,10 @@ class ServeConfig:
                 raise ValueError(f"--kv-offload-gb / KV_OFFLOAD_GB is not supported with tensor parallelism (tp = "
                                  f"{self.tp}): run with --tp 1 (data parallelism, --dp N, works: every replica has its "
                                  "own host tier), or set it to 0")
+        if parse_quantization(self.quantization) != "none" and self.tp > 1:
+            raise ValueError(f"--quantization {self.quantization} / QUANTIZATION is not supported with tensor "
+                             f"parallelism (tp = {self.tp}): the row scales are not sharded; run with --tp 1 (data "
+                             "parallelism, --dp N, works), or set it to none")
         return self
 
     def to_json(self) -> str:
