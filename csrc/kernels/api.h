@@ -296,6 +296,14 @@ hipError_t dsse_kv_pages(int gather, int n, void* k_cache, void* v_cache, const 
 // 2 L segments of page src are copied onto page dst.  Destinations are distinct and none is a source (the host checks).
 hipError_t dsse_kv_pages_copy(int n, void* k_cache, void* v_cache, const int* pairs, int L, int num_blocks,
                               unsigned seg_bytes, hipStream_t st);
+// Multi-LoRA products (lora.hip): row i uses adapter slot row_adapter[i] (-1: none).  A = [nslots, SR, K] bf16,
+// t = [M, SR] fp32; B = [nslots, N, R] bf16 (R in 8 / 16 / 32 / 64), scale = [nslots] fp32, slice_of_row = [N] in
+// [0, S), S <= 3, SR = S R; out = [M, N] fp32 (out_f32) or bf16, rows with -1 untouched.
+hipError_t dsse_lora_shrink(int M, int K, int SR, int nslots, const void* x, const void* A, const int* row_adapter,
+                            float* t, hipStream_t st);
+hipError_t dsse_lora_expand(int M, int N, int R, int S, int nslots, int out_f32, const float* t, const void* B,
+                            const float* scale, const int* row_adapter, const int* slice_of_row, void* out,
+                            hipStream_t st);
 // TP all-reduce + residual + RMSNorm over IPC peer buffers (allreduce.hip)
 size_t dsse_ar_buffer_bytes(int rows, int H);
 hipError_t dsse_ar_alloc(size_t bytes, void** ptr, void* handle64, int* uncached);
@@ -316,6 +324,7 @@ hipError_t dsse_check_sampler(int* out, int clear);
 hipError_t dsse_check_gemm_tiled(int* out, int clear);
 hipError_t dsse_check_kv_pages(int* out, int clear);
 hipError_t dsse_check_gemm_w8(int* out, int clear);
+hipError_t dsse_check_lora(int* out, int clear);
 // Stamps build: bind the step-anatomy record buffer (common.h stamps::) of a kernel file; no-ops otherwise.
 hipError_t dsse_stamps_bind_gemm_stream(void* rec);
 hipError_t dsse_stamps_bind_elementwise(void* rec);

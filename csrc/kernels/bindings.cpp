@@ -1858,6 +1858,53 @@ void kv_pages_copy(Tensor& k_cache, Tensor& v_cache, const Tensor& pairs) {
                                     (int)nb, (unsigned)seg, cur_stream()));
 }
 
+// ---- multi-LoRA (lora.hip): t = A_slot(i) x[i]; out[i] += scale_slot(i) B_slot(i) t[i, slice]; slot -1 = no adapter
+void lora_shrink(const Tensor& x, const Tensor& A, const Tensor& row_adapter, Tensor& t) {
+  for (const Tensor* p : {&x, &A, &row_adapter, (const Tensor*)&t}) check_gpu(*p, "lora_shrink operand");
+  check_dtype(x, at::kBFloat16, "x");
+  check_dtype(A, at::kBFloat16, "A");
+  check_dtype(row_adapter, at::kInt, "row_adapter");
+  check_dtype(t, at::kFloat, "t");
+  TORCH_CHECK(x.dim() == 2 && A.dim() == 3 && t.dim() == 2, "lora_shrink: x [M, K], A [slots, SR, K], t [M, SR]");
+  const int64_t M = x.size(0), K = x.size(1), SR = A.size(1);
+  TORCH_CHECK(A.size(0) >= 1 && A.size(2) == K && t.size(0) == M && t.size(1) == SR && row_adapter.numel() >= M,
+              "lora_shrink: shape mismatch");
+  TORCH_CHECK(K % 8 == 0 && SR % 8 == 0 && SR <= 192, "lora_shrink: K and S*R must be multiples of 8, S*R <= 192");
+  TORCH_CHECK(x.is_contiguous() && A.is_contiguous() && t.is_contiguous() && row_adapter.is_contiguous(),
+              "lora_shrink: operands must be contiguous");
+  for (const Tensor* p : {&x, &A, (const Tensor*)&t})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p->data_ptr()) % 16 == 0, "lora_shrink: tensors must be 16-byte aligned");
+  DSSE_CHECK_HIP(dsse_lora_shrink((int)M, (int)K, (int)SR, (int)A.size(0), x.data_ptr(), A.data_ptr(),
+                                  row_adapter.data_ptr<int>(), t.data_ptr<float>(), cur_stream()));
+}
+
+void lora_expand_add(const Tensor& t, const Tensor& B, const Tensor& scale, const Tensor& row_adapter,
+                     const Tensor& slice_of_row, Tensor& out) {
+  for (const Tensor* p : {&t, &B, &scale, &row_adapter, &slice_of_row, (const Tensor*)&out})
+    check_gpu(*p, "lora_expand_add operand");
+  check_dtype(t, at::kFloat, "t");
+  check_dtype(B, at::kBFloat16, "B");
+  check_dtype(scale, at::kFloat, "scale");
+  check_dtype(row_adapter, at::kInt, "row_adapter");
+  check_dtype(slice_of_row, at::kInt, "slice_of_row");
+  TORCH_CHECK(out.scalar_type() == at::kFloat || out.scalar_type() == at::kBFloat16, "out must be fp32 or bf16");
+  TORCH_CHECK(t.dim() == 2 && B.dim() == 3 && out.dim() == 2, "lora_expand_add: t [M, SR], B [slots, N, R], out [M, N]");
+  const int64_t M = out.size(0), N = out.size(1), R = B.size(2), SR = t.size(1);
+  TORCH_CHECK(R == 8 || R == 16 || R == 32 || R == 64, "lora_expand_add: pool rank must be 8, 16, 32 or 64");
+  TORCH_CHECK(SR % R == 0 && SR / R >= 1 && SR / R <= 3, "lora_expand_add: t must hold 1 to 3 slices of R columns");
+  TORCH_CHECK(B.size(0) >= 1 && B.size(1) == N && t.size(0) == M && scale.numel() == B.size(0) &&
+                  row_adapter.numel() >= M && slice_of_row.numel() == N, "lora_expand_add: shape mismatch");
+  TORCH_CHECK(t.is_contiguous() && B.is_contiguous() && out.is_contiguous() && scale.is_contiguous() &&
+                  row_adapter.is_contiguous() && slice_of_row.is_contiguous(),
+              "lora_expand_add: operands must be contiguous");
+  for (const Tensor* p : {&t, &B})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p->data_ptr()) % 16 == 0, "lora_expand_add: tensors must be 16-byte aligned");
+  DSSE_CHECK_HIP(dsse_lora_expand((int)M, (int)N, (int)R, (int)(SR / R), (int)B.size(0),
+                                  out.scalar_type() == at::kFloat ? 1 : 0, t.data_ptr<float>(), B.data_ptr(),
+                                  scale.data_ptr<float>(), row_adapter.data_ptr<int>(), slice_of_row.data_ptr<int>(),
+                                  out.data_ptr(), cur_stream()));
+}
+
 int64_t kernels_abi_version() { return 16; }
 
 // The dispatch's choice for an (M, N, K) projection: (impl, tiled cfg, split, fix, model estimate in us) -- impl as
@@ -1897,20 +1944,21 @@ bool kernels_checked() { return true; }
 bool kernels_checked() { return false; }
 #endif
 
-// Checked build: [9, 4] int32 (line, value, bound, count) of the first out-of-range index per kernel file,
+// Checked build: [10, 4] int32 (line, value, bound, count) of the first out-of-range index per kernel file,
 // in the order of kCheckFiles; all zeros in the default build.  Synchronises the device.
-const char* const kCheckFiles[9] = {"gemm_skinny.hip", "gemm_stream.hip", "attention.hip", "attention_prefill.hip",
+const char* const kCheckFiles[10] = {"gemm_skinny.hip", "gemm_stream.hip", "attention.hip", "attention_prefill.hip",
                                     "elementwise.hip", "sampler.hip", "gemm_tiled.hip", "kv_pages.hip",
-                                    "gemm_w8.hip"};
+                                    "gemm_w8.hip", "lora.hip"};
 Tensor kernel_checks(bool clear) {
   using Reader = hipError_t (*)(int*, int);
-  static const Reader readers[9] = {dsse_check_gemm_skinny, dsse_check_gemm_stream, dsse_check_attention,
+  static const Reader readers[10] = {dsse_check_gemm_skinny, dsse_check_gemm_stream, dsse_check_attention,
                                     dsse_check_attention_prefill, dsse_check_elementwise, dsse_check_sampler,
-                                    dsse_check_gemm_tiled, dsse_check_kv_pages, dsse_check_gemm_w8};
-  Tensor out = at::zeros({9, 4}, at::kInt);
+                                    dsse_check_gemm_tiled, dsse_check_kv_pages, dsse_check_gemm_w8,
+                                     dsse_check_lora};
+  Tensor out = at::zeros({10, 4}, at::kInt);
   if (!kernels_checked()) return out;
   DSSE_CHECK_HIP(hipDeviceSynchronize());
-  for (int i = 0; i < 9; ++i) DSSE_CHECK_HIP(readers[i](out.data_ptr<int>() + 4 * i, clear ? 1 : 0));
+  for (int i = 0; i < 10; ++i) DSSE_CHECK_HIP(readers[i](out.data_ptr<int>() + 4 * i, clear ? 1 : 0));
   return out;
 }
 // Stamps build: step-anatomy records (common.h stamps::record) of the ring GEMMs and RMSNorms.  step_stamps_arm
@@ -2051,6 +2099,9 @@ TORCH_LIBRARY(dsse, m) {
         "Tensor(c!) epoch, Tensor(d!) err, Tensor? part=None, int nsplit=0) -> ()");
   m.def("ar_gather(Tensor cand, Tensor(a!) out, Tensor peers, int rank, int rows, int H, Tensor(b!) gepoch, "
         "Tensor(c!) err) -> ()");
+  m.def("lora_shrink(Tensor x, Tensor A, Tensor row_adapter, Tensor(a!) t) -> ()");
+  m.def("lora_expand_add(Tensor t, Tensor B, Tensor scale, Tensor row_adapter, Tensor slice_of_row, "
+        "Tensor(a!) out) -> ()");
   m.def("kernels_abi_version() -> int", &kernels_abi_version);
   m.def("gemm_plan(int M, int N, int K, bool slab_consumer=False) -> (int, int, int, bool, float)", &gemm_plan);
   m.def("gemm_fix_timeouts(int device=0) -> int", &gemm_fix_timeouts);
@@ -2103,6 +2154,8 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("logprob_stats", &logprob_stats);
   m.impl("logprob_chosen", &logprob_chosen);
   m.impl("logprob_finish", &logprob_finish);
+  m.impl("lora_shrink", &lora_shrink);
+  m.impl("lora_expand_add", &lora_expand_add);
   m.impl("ar_rmsnorm", &ar_rmsnorm);
   m.impl("ar_gather", &ar_gather);
 }

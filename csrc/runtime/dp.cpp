@@ -51,6 +51,7 @@ std::string encode_request(const ChatRequest& r) {
   w.u8(r.guide_json ? 1 : 0);
   w.u8(r.guide_schema ? 1 : 0);
   w.i32(r.n);
+  w.str(r.lora);
   return w.data();
 }
 
@@ -91,6 +92,8 @@ bool decode_request(Reader& rd, ChatRequest* r) {
   r->guide_schema = rd.u8() != 0;
   r->n = rd.i32();
   if (r->n < 1 || r->n > 16) return false;
+  r->lora = rd.str();
+  if (r->lora.size() > 256) return false;
   return rd.good();
 }
 }  // namespace dpwire

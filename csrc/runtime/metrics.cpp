@@ -161,6 +161,22 @@ std::string Metrics::render() const {
     line(o, "engine_prefix_cache_offload_hit_tokens_total", "Prompt tokens served from the host tier", "counter",
          engine_prefix_cache_offload_hit_tokens_total.get());
   }
+  {
+    std::lock_guard<std::mutex> g(lora_mu_);
+    if (!lora_requests_.empty()) {
+      o += "# HELP lora_requests_total Chat requests that selected a LoRA adapter, per adapter name\n"
+           "# TYPE lora_requests_total counter\n";
+      for (const auto& kv : lora_requests_) {
+        std::string name;
+        for (char ch : kv.first) {  // label value escapes of the exposition format
+          if (ch == '\\' || ch == '"') name += '\\';
+          if (ch == '\n') name += "\\n";
+          else name += ch;
+        }
+        o += "lora_requests_total{adapter=\"" + name + "\"} " + std::to_string(kv.second) + "\n";
+      }
+    }
+  }
   line(o, "dp_workers_alive", "Data-parallel engine workers with a live heartbeat", "gauge", dp_workers_alive.get());
   line(o, "dp_requests_routed_total", "Chat requests routed to data-parallel engine workers", "counter",
        dp_requests_routed_total.get());

@@ -125,6 +125,11 @@ class Metrics {
     if (hits > 0) engine_prefix_cache_hits_total.add(hits);
     if (evictions > 0) engine_prefix_cache_evictions_total.add(evictions);
   }
+  // LoRA: chat requests accepted per adapter name (the base model is not counted); present once one was seen
+  void observe_lora_request(const std::string& adapter) {
+    std::lock_guard<std::mutex> g(lora_mu_);
+    ++lora_requests_[adapter];
+  }
   // data-parallel router (dp.h)
   Gauge dp_workers_alive;
   Counter dp_requests_routed_total;
@@ -143,6 +148,8 @@ class Metrics {
 
  private:
   mutable std::mutex extra_mu_;
+  mutable std::mutex lora_mu_;
+  std::map<std::string, uint64_t> lora_requests_;
   std::map<std::string, std::function<std::string()>> extra_;
 };
 

@@ -55,6 +55,7 @@ py::dict request_dict(const ChatRequest& r) {
   d["from_edge"] = r.from_edge;
   d["n"] = r.n;  // choices of this prompt (parallel sampling; 1 unless /v1/chat/completions asked for more)
   d["messages"] = r.messages_json;
+  d["lora"] = r.lora;  // the adapter "model" named ("" = the base model)
   return d;
 }
 
@@ -89,6 +90,8 @@ class Runtime {
     c.replay_max = (size_t)geti("replay_max", (int)c.replay_max);
     c.retention_s = geti("retention_s", c.retention_s);
     c.ui_html = gets("ui_html", "");
+    c.enable_lora = cfg.contains("enable_lora") && cfg["enable_lora"].cast<bool>();
+    if (cfg.contains("lora_names")) c.lora_names = cfg["lora_names"].cast<std::vector<std::string>>();
     BusConfig bc;
     bc.replay_max = c.replay_max;
     bc.retention_s = c.retention_s;

@@ -485,6 +485,24 @@ bool parse_sampling(const std::map<std::string, JsonValue>& o, ChatRequest& r, s
   return parse_controls(o, r, vocab, err) && parse_guide(o, r, err);
 }
 
+// "model" of a chat body.  LoRA off: any string is echoed (absent or empty: the served model's name).  LoRA on: an
+// adapter's name selects it (r.lora), the served model's name or an absent field selects none, anything else is
+// refused: false, with vLLM's message in *err (-> 404 model_not_found).
+bool resolve_model(const ServerConfig& cfg, const std::map<std::string, JsonValue>& o, ChatRequest& r,
+                   std::string* echo, std::string* err) {
+  auto mo = o.find("model");
+  const bool given = mo != o.end() && mo->second.kind == JsonValue::kString && !mo->second.str.empty();
+  *echo = given ? mo->second.str : cfg.model_name;
+  if (!cfg.enable_lora || !given || mo->second.str == cfg.model_name) return true;
+  if (std::find(cfg.lora_names.begin(), cfg.lora_names.end(), mo->second.str) == cfg.lora_names.end()) {
+    *err = "The model `" + mo->second.str + "` does not exist.";
+    return false;
+  }
+  r.lora = mo->second.str;
+  metrics().observe_lora_request(r.lora);
+  return true;
+}
+
 std::string http_error(int code, const std::string& msg, bool ka) {
   return simple_response(code, msg + "\n", "text/plain; charset=utf-8", ka, {"X-Content-Type-Options: nosniff"});
 }
@@ -959,8 +977,14 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   if (req.path == "/v1/models") {
     const std::string body = "{\"object\":\"list\",\"data\":[{\"id\":" + json_quote(model) +
                              ",\"object\":\"model\",\"created\":" + std::to_string((long long)time(nullptr)) +
-                             ",\"owned_by\":\"dsse\",\"root\":" + json_quote(model) + ",\"parent\":null}]}";
-    write_raw(c, simple_response(200, body, "application/json", ka));
+                             ",\"owned_by\":\"dsse\",\"root\":" + json_quote(model) + ",\"parent\":null}";
+    std::string adapters;  // then one entry per LoRA adapter, its parent the base model (as vLLM lists them)
+    for (const auto& name : srv_.config().lora_names)
+      adapters += ",{\"id\":" + json_quote(name) + ",\"object\":\"model\",\"created\":" +
+                  std::to_string((long long)time(nullptr)) + ",\"owned_by\":\"dsse\",\"root\":" + json_quote(name) +
+                  ",\"parent\":" + json_quote(model) + "}";
+    const std::string list = body + adapters + "]}";
+    write_raw(c, simple_response(200, list, "application/json", ka));
     return;
   }
   auto bad = [&](int code, const std::string& m) {
@@ -1105,10 +1129,19 @@ void IoThread::handle_openai(Conn& c, HttpRequest& req) {
   }
   r.from_edge = true;
   r.n = n_choices;
-  auto mo = o.find("model");
+  std::string oa_model;
+  {
+    std::string model_err;
+    if (!resolve_model(srv_.config(), o, r, &oa_model, &model_err)) {
+      write_raw(c, simple_response(404, "{\"object\":\"error\",\"message\":" + json_quote(model_err) +
+                                            ",\"type\":\"NotFoundError\",\"param\":null,\"code\":\"model_not_found\"}",
+                                   "application/json", ka));
+      return;
+    }
+  }
   c.openai = true;
   c.oa_stream = stream;
-  c.oa_model = (mo != o.end() && mo->second.kind == JsonValue::kString && !mo->second.str.empty()) ? mo->second.str : model;
+  c.oa_model = oa_model;
   c.oa_created = (int64_t)time(nullptr);
   c.oa_max_tokens = r.max_tokens;
   c.oa_choices.assign((size_t)n_choices, Conn::OaChoice{});
@@ -1457,6 +1490,11 @@ void IoThread::handle_request(Conn& c, HttpRequest& req) {
         write_raw(c, http_error(400, perr, ka));
         return;
       }
+      std::string echo;
+      if (!resolve_model(srv_.config(), o, r, &echo, &perr)) {
+        write_raw(c, http_error(404, perr, ka));
+        return;
+      }
       srv_.submit_chat(std::move(r));
       write_raw(c, simple_response(200, "{\"conversation_id\":" + json_quote(conv) + ",\"status\":\"streaming\"}\n",
                                    "application/json", ka));
@@ -1509,6 +1547,13 @@ void IoThread::handle_request(Conn& c, HttpRequest& req) {
     if (!parse_sampling(o, sampling, &perr, srv_.vocab_size())) {  // before any SSE byte: a bad parameter is a plain 400
       write_raw(c, http_error(400, perr, ka));
       return;
+    }
+    {
+      std::string echo;
+      if (!resolve_model(srv_.config(), o, sampling, &echo, &perr)) {
+        write_raw(c, http_error(404, perr, ka));
+        return;
+      }
     }
     std::string conv = ci == o.end() ? "" : ci->second.str;
     if (conv.empty()) conv = uuid4();

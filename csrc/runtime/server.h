@@ -73,6 +73,10 @@ struct ServerConfig {
   std::string ui_html;  // served at GET / when non-empty
   // POST /v1/chat/completions: the largest `n` (choices per request) it accepts, min(16, the engine's decode slots)
   int max_choices = 16;
+  // LoRA (--enable-lora): the loaded adapters' names.  With it on, "model" of a chat request selects an adapter (its
+  // name), the base model (model_name, or absent), or is refused with 404 model_not_found; off: any string is echoed
+  bool enable_lora = false;
+  std::vector<std::string> lora_names;
 };
 
 // Chat request handed to the engine (or the stub generator).
@@ -112,6 +116,7 @@ struct ChatRequest {
   // OpenAI chat (POST /v1/chat/completions): the conversation as normalised JSON
   // [{"role":..,"content":..},..]; empty = `message` is a single user turn
   std::string messages_json;
+  std::string lora;  // name of the LoRA adapter the request selected with "model" ("" = the base model)
 };
 
 // Conversation id (= bus subject) of choice i of a request: the id itself for choice 0.

@@ -40,6 +40,7 @@ only reused by work enqueued after the stop, so stream order makes reuse safe.
 """
 from __future__ import annotations
 
+import hashlib
 import itertools
 import math
 import os
@@ -97,6 +98,9 @@ class SamplingParams:
     # (docs/kernels.md, "Sampler"), or a viable prefix of one when max_tokens ends the stream first.  A pushdown walk
     # inside the same two guide passes; it takes no pattern pool entry.  Mutually exclusive with `guide`.
     json_object: bool = False
+    # the name of a loaded LoRA adapter (engine/lora.py; None: the base model).  The adapter travels with the
+    # params: through preemption and re-prefill, and to the siblings of an n > 1 request
+    lora: str | None = None
 
     def penalised(self) -> bool:
         return self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
@@ -401,6 +405,8 @@ class LLMEngine:
         self._pen_live = False  # the device's penalty block holds a non-neutral slot (then _upload rewrites it)
         self._lp_live = False   # the device's lp_meta holds a slot that is on (likewise)
         self._ctl_live = False  # the device's ctl_meta holds a non-neutral slot (likewise)
+        self._lora_live = False  # the device's slot_adapter holds a slot with an adapter (likewise)
+        self.lora_requests: dict = {}  # adapter name -> sequences queued under it
         # guided decoding: compiled patterns (pattern -> (table uint16 [n, 256], accept uint8 [n])), and the device
         # pool's entries: pattern -> index, references by live sequences per index, and the resident pattern per index
         # (an entry without references stays resident until another pattern needs it)
@@ -523,6 +529,11 @@ class LLMEngine:
                 raise ValueError("json_object cannot be combined with a guide (guided_regex / guided_choice)")
             if self.r.guide_pieces is None:
                 raise ValueError("JSON mode needs the vocabulary's pieces (ModelRunner.set_guide_vocab)")
+        if p.lora is not None:
+            if self.r.lora is None:
+                raise ValueError(f"LoRA adapter {p.lora!r} requested, but the engine was started without LoRA")
+            self.r.lora.slot_of(p.lora)  # (LoraError, a ValueError, for a name that is not loaded: nothing is queued)
+            self.lora_requests[p.lora] = self.lora_requests.get(p.lora, 0) + 1
         if p.guide_schema and p.guide is None:
             raise ValueError("guide_schema needs the lowered pattern in guide")
         if p.guide is not None:
@@ -655,6 +666,14 @@ class LLMEngine:
                 ctl[2 * Bm + i] = s.orig_len + p.min_tokens if bans else 0
                 ctl[3 * Bm:].view(np.float32)[i] = min(max(float(p.min_p), 0.0), 1.0)
             self._ctl_live = bool(live)
+        # slot_adapter (-1 = the base model, else the pool slot): likewise, from the first sequence with an adapter
+        adp = None
+        live = [(i, s) for i, s in enumerate(self.slots) if s is not None and s.params.lora is not None]
+        if live or self._lora_live:
+            adp = np.full(Bm, -1, dtype=np.int32)
+            for i, s in live:
+                adp[i] = self._adapter_slot(s)
+            self._lora_live = bool(live)
         bt_rows = {}
         for i in self._dirty_slots:
             s = self.slots[i]
@@ -677,6 +696,8 @@ class LLMEngine:
             put(r.lp_meta, torch.from_numpy(lpm))
         if ctl is not None:
             put(r.ctl_meta, torch.from_numpy(ctl))
+        if adp is not None:
+            put(r.slot_adapter, torch.from_numpy(adp))
         for i, row in bt_rows.items():
             put(r.block_tables[i], row)
         self._dirty_slots.clear()
@@ -698,6 +719,19 @@ class LLMEngine:
             packed = packed.pin_memory().to(r.device, non_blocking=True)
         n = len(idx)
         r.block_tables.view(-1).index_copy_(0, packed[:n].long(), packed[n:])
+
+    def _adapter_slot(self, s: Sequence) -> int:
+        """The LoRA pool slot of s's adapter (-1: the base model)."""
+        return -1 if s.params.lora is None else self.r.lora.slot_of(s.params.lora)
+
+    @staticmethod
+    def _hash_salt(s: Sequence) -> bytes:
+        """h_{-1} of s's page-hash chain: empty for the base model, a digest of the adapter's NAME otherwise (K and V
+        depend on the adapter, so its pages must never serve another adapter or the base model; the name, not the
+        slot, so the identity survives slot numbering).  The host tier sits behind the same hashes."""
+        if s.params.lora is None:
+            return b""
+        return hashlib.blake2b(b"lora:" + s.params.lora.encode(), digest_size=16).digest()
 
     def _bias(self, p: SamplingParams) -> dict:
         """logit_bias as {id: bias} over the ids the vocabulary has (ids distinct: the kernel's contract)."""
@@ -815,7 +849,8 @@ class LLMEngine:
         full = s.prompt[:s.orig_len] + s.out_ids
         pages = min(min(len(s.prompt) + s.decode_enqueued, len(full)) // PAGE, len(s.blocks))
         if pages > len(s.hashes):
-            s.hashes = s.hashes + page_hashes(full[:pages * PAGE], s.hashes[-1] if s.hashes else b"", len(s.hashes))
+            s.hashes = s.hashes + page_hashes(full[:pages * PAGE], s.hashes[-1] if s.hashes else self._hash_salt(s),
+                                              len(s.hashes))
         self._publish_pages(s, pages)
 
     def _check_write_pages(self, chunks: list, dec: list) -> None:
@@ -905,13 +940,13 @@ class LLMEngine:
             hits, run, host = [], None, []
             if par is not None:
                 if self.prefix_cache and not s.hashes:
-                    s.hashes = page_hashes(s.prompt)
+                    s.hashes = page_hashes(s.prompt, self._hash_salt(s))
             elif self.prefix_cache:
                 # the resident leading pages of the prompt minus its last token: at least one token is always
                 # prefilled, so the first token is sampled by the ordinary last-chunk path.  (Hashed once; looked up
                 # on every attempt while it waits: the index changes between steps.)
                 if not s.hashes:
-                    s.hashes = page_hashes(s.prompt)
+                    s.hashes = page_hashes(s.prompt, self._hash_salt(s))
                 chain = s.hashes[:(len(s.prompt) - 1) // PAGE]
                 if self.offload is None:
                     hits = self.alloc.lookup(chain)
@@ -987,6 +1022,8 @@ class LLMEngine:
                 r.set_history(s.slot, s.prompt, s.orig_len)
             if s.params.logprobs >= 0:
                 r.enable_logprobs()  # (the first such request captures the graph twins with the logprob passes)
+            if s.params.lora is not None:
+                r.enable_lora()  # (the first such request captures the graph twins with the LoRA layer body)
             if s.params.controlled():
                 # its bias entries and banned ids (again after a preemption: the slot may be another one); the first
                 # such request captures the graph twins with the bias and ban pass and min_p
@@ -1126,7 +1163,7 @@ class LLMEngine:
                 s.admit_ns = time.time_ns()
             last = s.prefilled + n == len(s.prompt)
             chunks.append(PrefillSeq(slot=s.slot, tokens=s.prompt[s.prefilled:s.prefilled + n], start_pos=s.prefilled,
-                                     block_table=s.blocks, last_chunk=last))
+                                     block_table=s.blocks, last_chunk=last, adapter=self._adapter_slot(s)))
             s.prefilled += n
             budget -= n
             if last:

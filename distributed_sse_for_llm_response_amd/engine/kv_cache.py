@@ -67,8 +67,9 @@ def page_hashes(tokens, prev: bytes = b"", first: int = 0) -> list:
     """Content hashes of the full pages of `tokens` from page `first` on: a chain, h_i = blake2b(h_{i-1} ||
     int32 bytes of tokens[32 i : 32 i + 32], 16-byte digest) with h_{-1} empty (`prev` = h_{first-1}), so a page's hash
     names the whole prefix up to and including it.  A 128-bit digest is treated as collision-free: two different
-    prefixes with one hash would share KV pages, at odds of ~2^-128 per pair.  Nothing but the token ids feeds the KV
-    (one model, no adapters), so there is no salt."""
+    prefixes with one hash would share KV pages, at odds of ~2^-128 per pair.  Besides the token ids only a LoRA adapter feeds the KV: a
+    sequence under an adapter starts its chain from a digest of the adapter's name as `prev` (LLMEngine._hash_salt), so
+    its pages never serve another adapter or the base model; base-model chains start from the empty `prev`."""
     n = len(tokens) // PAGE
     raw = memoryview(array("i", tokens[PAGE * first:PAGE * n]).tobytes())  # (int32, native = little-endian here)
     out = []

@@ -186,6 +186,7 @@ class PrefillSeq:
     start_pos: int          # absolute position of tokens[0]
     block_table: list       # the sequence's full block table
     last_chunk: bool        # sample a token after this chunk
+    adapter: int = -1       # LoRA pool slot of the sequence (-1: the base model)
 
 
 class SampleSite(NamedTuple):
@@ -209,7 +210,7 @@ class SampleSite(NamedTuple):
 class ModelRunner:
     def __init__(self, w: EngineWeights, num_blocks: int, max_batch: int = 64, max_model_len: int = 4096,
                  max_prefill_tokens: int = 8192, device="cuda", comm: TPComm | None = None, use_graphs=None,
-                 kv_cache_dtype="auto", quantization=None):
+                 kv_cache_dtype="auto", quantization=None, lora=None):
         # quantization "fp8": FP8 (e4m3) weights beside a widened bf16 copy (engine/weights.py).  Decode buckets of
         # W8_MAX_M rows or fewer run every projection and the LM head on the FP8 kernels over *_q; wider buckets,
         # prefill, mixed steps and the first-token head use the existing kernels over the widened *_t -- identical
@@ -223,6 +224,15 @@ class ModelRunner:
         self.w, self.cfg = w, w.cfg
         self.device = torch.device(device)
         self.comm = comm or TPComm()
+        # lora: an engine.lora.LoraPool on this device.  Until the first request that names an adapter nothing
+        # changes; from then on every step runs the LoRA layer body (_lora_layers) in twins of the captured graphs
+        if lora is not None:
+            if self.comm.size > 1:
+                raise ValueError("LoRA is not supported with tensor parallelism (tp > 1)")
+            if self.w8:
+                raise ValueError("LoRA is not supported with quantization=fp8")
+        self.lora = lora
+        self.lora_used = False  # a request ever named an adapter (then the LoRA body is launched / captured)
         self.max_batch = max_batch
         self.max_model_len = max_model_len
         self.max_blocks = math.ceil(max_model_len / PAGE) + 1
@@ -252,6 +262,8 @@ class ModelRunner:
         self.active = self.slot_meta[:Bm]
         self.block_tables = torch.zeros(Bm, self.max_blocks, **i32)
         self.slots = torch.full((Bm,), -1, **i32)
+        # LoRA pool slot per decode slot (-1: none), host-owned and uploaded like lp_meta (LLMEngine._upload)
+        self.slot_adapter = torch.full((Bm,), -1, **i32)
         self.ctx_len = torch.zeros(Bm, **i32)
         self.q_len = torch.zeros(Bm, **i32)
         self.q_start = torch.arange(Bm, **i32)
@@ -316,6 +328,12 @@ class ModelRunner:
         self.attn = torch.zeros(Bm, nh * 128, **bf)
         self.h = torch.zeros(Bm, F, **bf)
         self.tmp = torch.zeros(Bm, H, **bf)
+        if lora is not None:
+            # the LoRA body's unfused outputs (decode rows) and the shrink result t [rows, S·R] of any pass
+            self.lora_qkv = torch.zeros(Bm, (nh + 2 * nkv) * 128, **bf)
+            self.lora_gu = torch.zeros(Bm, 2 * F, **bf)
+            self._lora_t = torch.zeros(max(Bm, min(max(PREFILL_GRAPH_BUCKETS), max_prefill_tokens)) * 3 * lora.R,
+                                       device=dev, dtype=torch.float32)
         # fp32 split-K slabs of the residual projections (reduced inside the next RMSNorm)
         # (on a GPU also large enough for the 8 slabs of a PREFILL_SLAB_ROWS-row prompt pass: _prefill_resid)
         slab_floats = 32 * Bm * H
@@ -369,6 +387,15 @@ class ModelRunner:
         ops.rmsnorm(resid, w.layers[0].attn_norm, x, eps, embed=w.embed, ids=self.ids[r])
         part, nparts = decode_partitioning(B, nkv, self.max_model_len)
         nl = len(w.layers)
+        if self.lora_used:  # every bucket: the unfused body with the low-rank deltas
+            d = dict(resid=resid, x=x, q=self.q[r].view(B, nh, 128), attn=self.attn[r].view(B, nh, 128), h=self.h[r],
+                     tmp=self.tmp[r], qkv=self.lora_qkv[r], gu=self.lora_gu[r])
+            self._lora_layers(B, d, self.positions[r], self.slots[r], self.slot_adapter[r])
+            for b0 in range(0, B, 256):
+                ops.gemm_out(x[b0:b0 + 256], w.lm_head_t, self.logits[b0:min(B, b0 + 256)])
+            self._sample_commit(B)
+            ops.ring_advance(self.ring_counter)
+            return
         if B > DECODE_GEMM_MAX_M:
             self._decode_layers_wide(B, resid, x, part, nparts)
             return
@@ -437,6 +464,83 @@ class ModelRunner:
                                  self.kv.v[li], nh, nkv, self.split_part, self.block_tables[r], self.q_start[r],
                                  self.q_len[r], self.ctx_len[r], self.work_seq[r], self.work_tile[r], self.attn[r],
                                  self.part_o, self.part_ml, part, nparts, *self._kv_scales(li))
+
+    # ------------------------------------------------------------------ LoRA
+    def enable_lora(self) -> None:
+        """The first request that names an adapter: from now on every step (decode, prefill, mixed) runs the LoRA
+        layer body, in graph twins captured here; base-model rows ride in them with adapter -1."""
+        if self.lora is None:
+            raise ValueError("this engine was started without a LoRA pool (--enable-lora)")
+        if not self.lora_used:
+            if self.device.type == "cuda":
+                # the two kernels' first launch (code object load) happens here, eagerly, not inside the capture:
+                # one row without an adapter writes zeros to the t scratch and leaves the output untouched
+                none = torch.full((1,), -1, device=self.device, dtype=torch.int32)
+                self._lora_delta("qkv", 0, self.x[:1], self.lora_qkv[:1], none)
+                # and the unfused projections at every captured row count, into scratch buffers only (as capture()
+                # warms its shapes: kernel attributes and the dispatch's state are set outside the capture)
+                L, nh = self.w.layers[0], self.w.nh
+                rows = set(self.graphs) | set(self.pf_graphs) | {B + C for B, lst in self.mx_graphs.items() for C, _ in lst}
+                for m in sorted(rows):
+                    b = self.pf if self.pf is not None and m <= self.pf.tmax else None
+                    if b is None and m > self.max_batch:
+                        continue
+                    x, attn, h, tmp = ((b.x, b.attn, b.h, b.tmp) if b is not None else
+                                       (self.x, self.attn, self.h, self.tmp))
+                    qkv, gu = (b.qkv, b.gu) if b is not None else (self.lora_qkv, self.lora_gu)
+                    ops.gemm_out(x[:m], L.wqkv_t, qkv[:m])
+                    ops.gemm_out(attn[:m].view(m, nh * 128), L.wo_t, tmp[:m])
+                    ops.gemm_out(x[:m], L.wgu_t, gu[:m])
+                    ops.gemm_out(h[:m], L.wd_t, tmp[:m])
+                torch.cuda.synchronize(self.device)
+            self.lora_used = True
+            self._capture_twins()
+
+    def _lora_delta(self, p: str, li: int, x, out, ra) -> None:
+        """out += the rows' adapter deltas of projection p (qkv / o / gu / d) of layer li: one shrink over x for all
+        of the projection's slices, then the expand-add with the slice id of each output row."""
+        P = self.lora
+        M, SR = x.shape[0], P.A[p].shape[2]
+        t = self._lora_t[:M * SR].view(M, SR) if M * SR <= self._lora_t.numel() else \
+            torch.empty(M, SR, device=self.device, dtype=torch.float32)  # (an eager prompt pass above the buckets)
+        ops.lora_shrink(x, P.A[p][li], ra, t)
+        ops.lora_expand_add(t, P.B[p][li], P.scale, ra, P.slice_of_row[p], out)
+
+    def _lora_layers(self, B: int, d: dict, pos, slots, ra, split: bool = False) -> None:
+        """Every layer over M rows with per-row adapters `ra` (int32 [M], -1 = none): rows [0, B) are decode rows,
+        the rest the packed prompt rows that d's prefill metadata describes.  The fused kernels cannot take a delta
+        (they fold RoPE and the KV write into attention, SiLU·mul into the epilogue, the split-K sum into the norm), so
+        this body is built from the unfused ops: each projection's bf16 output, the delta added to it in place
+        (before RoPE / SiLU / the residual add), then the consumer.  One body for decode, prefill and mixed steps."""
+        w, eps = self.w, self.cfg.rms_eps
+        nh, nkv = w.nh, w.nkv
+        resid, x, q, attn, h, tmp, qkv, gu = (d[k] for k in ("resid", "x", "q", "attn", "h", "tmp", "qkv", "gu"))
+        M = x.shape[0]
+        r = slice(0, B)
+        dpart, dnparts = decode_partitioning(max(B, 1), nkv, self.max_model_len)
+        nl = len(w.layers)
+        for li, L in enumerate(w.layers):
+            kc, vc = self.kv.k[li], self.kv.v[li]
+            ops.gemm_out(x, L.wqkv_t, qkv)
+            self._lora_delta("qkv", li, x, qkv, ra)
+            ops.rope_kv_write(qkv, pos, slots, self.rope, q, kc, vc, nh, nkv, *self._kv_scales(li))
+            if B:
+                ops.paged_attention(0, q[r], kc, vc, self.block_tables[r], self.q_start[r], self.q_len[r],
+                                    self.ctx_len[r], self.work_seq[r], self.work_tile[r], attn[r], self.part_o,
+                                    self.part_ml, dpart, dnparts, *self._kv_scales(li))
+            if M > B:
+                self._prefill_attention(li, q, attn, d, split=split)
+            a2 = attn.view(M, nh * 128)
+            ops.gemm_out(a2, L.wo_t, tmp)
+            self._lora_delta("o", li, a2, tmp, ra)
+            ops.rmsnorm(resid, L.ffn_norm, x, eps, delta=tmp)
+            ops.gemm_out(x, L.wgu_t, gu)
+            self._lora_delta("gu", li, x, gu, ra)
+            ops.silu_mul(gu, h)
+            ops.gemm_out(h, L.wd_t, tmp)
+            self._lora_delta("d", li, h, tmp, ra)
+            w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
+            ops.rmsnorm(resid, w_next, x, eps, delta=tmp)
 
     def _kv_scales(self, li: int) -> tuple:
         """(k_scale, v_scale) of layer li's cache: trailing arguments of the cache ops (1.0, 1.0 for bf16)."""
@@ -722,8 +826,12 @@ class ModelRunner:
                           row_slot, self.guide_eos)
 
     def _twin_key(self) -> tuple:
-        """The pass set in use: (penalties, logprobs, the bias and ban pass / min_p, the guide passes)."""
-        return (self.hist_used, self.lp_used, self.ctl_used, self.guide_used)
+        """The pass set in use: (penalties, logprobs, the bias and ban pass / min_p, the guide passes), and a fifth
+        component, True, once the LoRA body is in use.  It is absent before, not False: the tests of the earlier
+        features pin the four-component values (tests/test_guided_cpu.py, test_guided_json_gpu.py, test_logprobs_gpu.py
+        and their kin compare _twin_key() and index _twins with 4-tuples).  A further component must follow the same
+        rule, appended after this one, and readers of the first four slice them (_slot_arrays)."""
+        return (self.hist_used, self.lp_used, self.ctl_used, self.guide_used) + ((True,) if self.lora_used else ())
 
     def _capture_graphs(self, shapes, body) -> list:
         """Capture body(shape) into a new graph in the shared pool, largest shape first (the first graph ever
@@ -755,7 +863,8 @@ class ModelRunner:
         """The first request that needs a new pass set (_twin_key): every captured graph gets a twin with the passes
         in use (_sample), replayed from now on; until then the graphs captured at startup run, which hold no such
         launch and no extra collective (an early-exit launch per step measured +8 us on the 4.23 ms 64-stream step:
-        profiles/r7/penalties.md).  The key names 15 pass sets besides the empty one, each captured at most once
+        profiles/r7/penalties.md).  The key names 15 pass sets besides the empty one (31 with a LoRA pool: each set
+        with and without the LoRA body), each captured at most once
         between two capture() calls.  Stream capture executes nothing, so no decode state changes; the shapes and
         buffers are the ones the startup capture warmed, and the logprob all-gathers run once eagerly first.
         Deterministic across a TP group: every rank admits the same request in the same step."""
@@ -779,7 +888,8 @@ class ModelRunner:
         self.twin_capture_s = time.perf_counter() - t0
         if self.comm.rank == 0:
             what = " and ".join(n for n, on in zip(("the penalty pass", "the logprob passes",
-                                                    "the bias and ban pass / min_p", "the guide passes"), key) if on)
+                                                    "the bias and ban pass / min_p", "the guide passes",
+                                                    "the LoRA layer body"), key) if on)
             print(f"[engine] first request with this combination: captured the graphs with {what} "
                   f"({self.twin_capture_s:.2f} s)", flush=True)
 
@@ -988,8 +1098,9 @@ class ModelRunner:
         """[(tensor, the dimension that indexes slots)]: the device state that travels with a sequence when its slot
         moves (the host-owned slot_meta / pen_meta are re-uploaded by the engine).  A feature's arrays travel once a
         request has used it; a new per-slot array needs one line here."""
-        hist, lp, ctl, guide = self._twin_key()
+        hist, lp, ctl, guide = self._twin_key()[:4]
         arrays = [(self.ids, 0), (self.positions, 0)]
+        arrays += [(self.slot_adapter, 0)] if self.lora_used else []
         arrays += [(self.hist_state, 0)] if hist else []  # the token histories: length word + tokens
         arrays += [(self.lp_meta, 0)] if lp else []
         arrays += [(self.ctl_body, 0), (self.ctl_meta.view(4, -1), 1)] if ctl else []  # bias / ban records + columns
@@ -1127,7 +1238,7 @@ class ModelRunner:
         dev = self.device
         n = len(seqs)
         # vectorised per sequence (an 8k-token chunk was ~25k Python list appends on the TTFT path)
-        ids_l, pos_l, slots_l = [], [], []
+        ids_l, pos_l, slots_l, adp_l = [], [], [], []
         q_start, q_len, ctx_len, items = [], [], [], []
         bt = torch.zeros(n, self.max_blocks, dtype=torch.int32)
         row = 0
@@ -1139,6 +1250,7 @@ class ModelRunner:
             ids_l.append(np.asarray(s.tokens, dtype=np.int64))
             pos_l.append(p)
             slots_l.append(table[p // PAGE] * PAGE + p % PAGE)
+            adp_l.append(np.full(m, s.adapter, dtype=np.int64))
             q_len.append(m)
             ctx_len.append(s.start_pos + m)
             bt[i, : len(s.block_table)] = torch.from_numpy(table.astype(np.int32))
@@ -1159,13 +1271,15 @@ class ModelRunner:
             [np.concatenate(ids_l) if ids_l else empty, np.concatenate(pos_l) if pos_l else empty,
              np.concatenate(slots_l) if slots_l else empty,
              np.asarray(q_start + q_len + ctx_len + work_seq + work_tile, dtype=np.int64),
-             fw.astype(np.int64), fc.astype(np.int64)]).astype(np.int32))
+             fw.astype(np.int64), fc.astype(np.int64),
+             np.concatenate(adp_l) if adp_l and self.lora_used else empty]).astype(np.int32))
         if dev.type == "cuda":
             meta = meta.pin_memory().to(dev, non_blocking=True)
             bt = bt.pin_memory().to(dev, non_blocking=True)
         d, o = {}, 0
         for name, k in (("ids", T), ("pos", T), ("slots", T), ("qs", n), ("ql", n), ("ctx", n),
-                        ("ws", len(work_seq)), ("wt", len(work_seq)), ("fw", len(fw)), ("fc", len(fc))):
+                        ("ws", len(work_seq)), ("wt", len(work_seq)), ("fw", len(fw)), ("fc", len(fc)),
+                        ("adp", T if self.lora_used else 0)):
             d[name], o = meta[o:o + k], o + k
         d["bt"] = bt
         d["fslots"] = plan[2] if plan else 0
@@ -1229,6 +1343,8 @@ class ModelRunner:
         d.update(resid=torch.empty(T, H, **f32), x=torch.empty(T, H, **bf), q=torch.empty(T, nh, 128, **bf),
                  attn=torch.empty(T, nh, 128, **bf), h=torch.empty(T, F, **bf), tmp=torch.empty(T, H, **bf),
                  qkv=torch.empty(T, (nh + 2 * nkv) * 128, **bf), part=math.ceil(max(ctx_len) / 32) * 32)
+        if self.lora_used:
+            d.update(gu=torch.empty(T, 2 * F, **bf))
         self._prefill_layers(T, d)
         self._prefill_sample(seqs, d["x"], q_start, q_len, ring_row)
 
@@ -1239,6 +1355,9 @@ class ModelRunner:
         resid, x, q, attn, h, tmp, qkv = (d[k] for k in ("resid", "x", "q", "attn", "h", "tmp", "qkv"))
         ops.rmsnorm(resid, w.layers[0].attn_norm, x, eps, embed=w.embed, ids=d["ids"])
         nl = len(w.layers)
+        if self.lora_used:
+            self._lora_layers(0, d, d["pos"], d["slots"], d["adp"], split=True)
+            return
         # projections on the engine's tiled-layout GEMMs (gemm_pipe.hip / gemm_tiled.hip for T > 128 rows; gate_up with
         # its fused SiLU·mul epilogue): no library GEMM
         for li, L in enumerate(w.layers):
@@ -1304,6 +1423,8 @@ class ModelRunner:
                  mx_ids=torch.empty(M, dtype=torch.int32, device=dev),
                  mx_pos=torch.empty(M, dtype=torch.int32, device=dev),
                  mx_slots=torch.empty(M, dtype=torch.int32, device=dev))
+        if self.lora_used:
+            d.update(gu=torch.empty(M, 2 * F, **bf), mx_adp=torch.empty(M, dtype=torch.int32, device=dev))
         self._mixed_body(B, T, d)
         self._prefill_sample(seqs, d["x"], q_start, q_len, ring_row)
 
@@ -1311,9 +1432,11 @@ class ModelRunner:
         """The graph body of a mixed step: bucket B decode rows + C static prompt rows (_PrefillStatic)."""
         d = self.pf.views(C)
         M = B + C
-        for k in ("resid", "x", "q", "attn", "h", "tmp", "qkv"):
+        for k in ("resid", "x", "q", "attn", "h", "tmp", "qkv") + (("gu",) if self.lora_used else ()):
             d[k] = getattr(self.pf, k)[:M]
         d.update(mx_ids=self.pf.mx_ids[:M], mx_pos=self.pf.mx_pos[:M], mx_slots=self.pf.mx_slots[:M])
+        if self.lora_used:
+            d.update(mx_adp=self.pf.mx_adp[:M])
         self._mixed_body(B, C, d)
 
     def _mixed_body(self, B: int, T: int, d: dict) -> None:
@@ -1337,18 +1460,24 @@ class ModelRunner:
         ops.rmsnorm(resid, w.layers[0].attn_norm, x, eps, embed=w.embed, ids=ids)
         dpart, dnparts = decode_partitioning(B, nkv, self.max_model_len)
         nl = len(w.layers)
-        for li, L in enumerate(w.layers):
-            kc, vc = self.kv.k[li], self.kv.v[li]
-            self._proj(x, L.wqkv_t, qkv)
-            ops.rope_kv_write(qkv, pos, slots, self.rope, q, kc, vc, nh, nkv, *self._kv_scales(li))
-            ops.paged_attention(0, q[r], kc, vc, self.block_tables[r], self.q_start[r], self.q_len[r],
-                                self.ctx_len[r], self.work_seq[r], self.work_tile[r], attn[r], self.part_o,
-                                self.part_ml, dpart, dnparts, *self._kv_scales(li))
-            self._prefill_attention(li, q, attn, d)
-            self._resid_proj(attn.view(M, nh * 128), L.wo_t, resid, L.ffn_norm, x, tmp)
-            self._gate_up(x, L, h)
-            w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
-            self._resid_proj(h, L.wd_t, resid, w_next, x, tmp)
+        if self.lora_used:  # decode rows: their slots' adapters; prompt rows: the uploaded per-row adapters
+            ra = d["mx_adp"]
+            ra[:B].copy_(self.slot_adapter[r])
+            ra[B:].copy_(d["adp"][:T])
+            self._lora_layers(B, d, pos, slots, ra)
+        else:
+            for li, L in enumerate(w.layers):
+                kc, vc = self.kv.k[li], self.kv.v[li]
+                self._proj(x, L.wqkv_t, qkv)
+                ops.rope_kv_write(qkv, pos, slots, self.rope, q, kc, vc, nh, nkv, *self._kv_scales(li))
+                ops.paged_attention(0, q[r], kc, vc, self.block_tables[r], self.q_start[r], self.q_len[r],
+                                    self.ctx_len[r], self.work_seq[r], self.work_tile[r], attn[r], self.part_o,
+                                    self.part_ml, dpart, dnparts, *self._kv_scales(li))
+                self._prefill_attention(li, q, attn, d)
+                self._resid_proj(attn.view(M, nh * 128), L.wo_t, resid, L.ffn_norm, x, tmp)
+                self._gate_up(x, L, h)
+                w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
+                self._resid_proj(h, L.wd_t, resid, w_next, x, tmp)
         ops.gemm_out(x[r], w.lm_head_t, self.logits[r])
         self._sample_commit(B)
         ops.ring_advance(self.ring_counter)
@@ -1371,11 +1500,13 @@ class _PrefillStatic:
         self.tile = runner.attn_tile  # query tokens per prompt-attention work item (64; fp8 cache: 64 / G)
         self.nw = tmax // self.tile + self.ns  # work items: sum of ceil(q_len / tile) <= T / tile + seqs
         self.mb = runner.max_blocks
+        self.lora = runner.lora is not None  # then the image carries the rows' adapter slots ("adp")
         n1 = self.ns + 1
         self.off = {}
         o = 0
         for name, k in (("ids", tmax), ("pos", tmax), ("slots", tmax), ("qs", n1), ("ql", n1), ("ctx", n1),
-                        ("ws", self.nw), ("wt", self.nw), ("bt", n1 * self.mb), ("samp", 3 * self.ns + 2)):
+                        ("ws", self.nw), ("wt", self.nw), ("bt", n1 * self.mb), ("samp", 3 * self.ns + 2),
+                        ("adp", tmax if self.lora else 0)):
             self.off[name] = (o, k)
             o += k
         self.words = o
@@ -1398,6 +1529,9 @@ class _PrefillStatic:
         # mixed steps: ids / positions / slots of the B decode rows followed by the chunk rows
         i32 = dict(device=dev, dtype=torch.int32)
         self.mx_ids, self.mx_pos, self.mx_slots = (torch.zeros(tmax, **i32) for _ in range(3))
+        if self.lora:  # the LoRA body's gate / up tile and the mixed step's per-row adapters
+            self.gu = torch.zeros(tmax, 2 * F, **bf)
+            self.mx_adp = torch.full((tmax,), -1, **i32)
         # first-token sampling inside the graph (ModelRunner._graph_sample): the finishing prompts' last rows, their
         # sampling parameters, logits, candidates and picks, ns rows each
         ns, V = self.ns, w.vocab_local
@@ -1423,6 +1557,8 @@ class _PrefillStatic:
              "qs": self._meta("qs"), "ql": self._meta("ql"), "ctx": self._meta("ctx"),
              "ws": self._meta("ws")[:nwb], "wt": self._meta("wt")[:nwb],
              "bt": self._meta("bt").view(self.ns + 1, self.mb), "part": self.part}
+        if self.lora:
+            d.update(adp=self._meta("adp")[:tb], gu=self.gu[:tb])
         d.update(resid=self.resid[:tb], x=self.x[:tb], q=self.q[:tb], attn=self.attn[:tb], h=self.h[:tb],
                  tmp=self.tmp[:tb], qkv=self.qkv[:tb])
         return d
@@ -1445,6 +1581,8 @@ class _PrefillStatic:
         ws, wt = (a[o[k][0]:o[k][0] + o[k][1]] for k in ("ws", "wt"))
         bt = a[o["bt"][0]:o["bt"][0] + o["bt"][1]].reshape(self.ns + 1, self.mb)
         slots[:] = -1
+        adp = a[o["adp"][0]:o["adp"][0] + o["adp"][1]]
+        adp[:] = -1
         q_start, q_len, items = [], [], []
         row = 0
         for i, s in enumerate(seqs):
@@ -1456,6 +1594,8 @@ class _PrefillStatic:
             pos[row:row + n] = p
             table = np.asarray(s.block_table, dtype=np.int64)
             slots[row:row + n] = table[p // PAGE] * PAGE + p % PAGE
+            if self.lora:
+                adp[row:row + n] = s.adapter
             bt[i, :len(s.block_table)] = s.block_table
             qs[i], ql[i], ctx[i] = row0 + row, n, s.start_pos + n
             # flash prefill: heaviest (most keys) 64-query tiles first (as _prefill_meta)

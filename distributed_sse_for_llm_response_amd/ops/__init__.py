@@ -191,6 +191,30 @@ def qkv_attention_decode_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_ca
     return 0
 
 
+# ---- multi-LoRA (csrc/kernels/lora.hip): every row names its adapter slot in row_adapter (int32, -1 = none)
+LORA_RANKS = (8, 16, 32, 64)  # pool ranks the expand kernel is built for
+LORA_MAX_SLOTS = 8
+
+
+def lora_shrink(x, A, row_adapter, t):
+    """t[M, S·R] (fp32) = A[row_adapter[i]] · x[i]: x [M, K] bf16, A [slots, S·R, K] bf16 (the stacked A matrices of a
+    fused projection: one pass over x).  Rows with adapter -1 get zeros."""
+    if _hip(x):
+        torch.ops.dsse.lora_shrink(x, A, row_adapter, t)
+    else:
+        ref.lora_shrink(x, A, row_adapter, t)
+
+
+def lora_expand_add(t, B, scale, row_adapter, slice_of_row, out):
+    """out[i, n] += scale[a] · Σ_j B[a][n, j] · t[i, slice_of_row[n]·R + j] with a = row_adapter[i]: B [slots, N, R]
+    bf16 in the engine's output-row order, scale [slots] fp32 (applied to the fp32 sum), out [M, N] fp32 or bf16.  Rows
+    with adapter -1 keep their bits."""
+    if _hip(out):
+        torch.ops.dsse.lora_expand_add(t, B, scale, row_adapter, slice_of_row, out)
+    else:
+        ref.lora_expand_add(t, B, scale, row_adapter, slice_of_row, out)
+
+
 def kernel_cfg_env(**overrides) -> str:
     """The DSSE_KERNEL_CFG string (the kernel library's one configuration override: "key=value,..."; keys in
     csrc/kernels/bindings.cpp env_int, e.g. gemm_impl, t_cfg, s_nw) with `overrides` merged into the current value.

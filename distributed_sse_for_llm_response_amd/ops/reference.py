@@ -1043,3 +1043,26 @@ def logprob_finish(rec_all, chosen_all, active, lp_meta, row_slot, lp_ring, ring
             ring_i[row, slot, 1 + rank] = tid if used else -1
             val = rec_all[k // LP_TOP, b, 2 + 2 * (k % LP_TOP)]
             lp_ring[row, slot, 1 + LP_TOP + rank] = val - lse if used and float(val) > _NEG_INF else _NEG_INF
+
+
+# ---------------------------------------------------------------- multi-LoRA (csrc/kernels/lora.hip)
+def lora_shrink(x, A, row_adapter, t):
+    """t[i] = A[row_adapter[i]] · x[i] in fp32 (A [slots, S·R, K]); rows with adapter -1 get zeros."""
+    M = x.shape[0]
+    ra = row_adapter[:M].long()
+    t.zero_()
+    for a in sorted(set(ra.tolist()) - {-1}):
+        rows = (ra == a).nonzero().flatten()
+        t[rows] = x[rows].float() @ A[a].float().t()
+
+
+def lora_expand_add(t, B, scale, row_adapter, slice_of_row, out):
+    """out[i, n] += scale[a] · Σ_j B[a][n, j] · t[i, slice_of_row[n]·R + j], a = row_adapter[i]; rows with adapter -1
+    keep their bits.  The scale multiplies the fp32 sum; the result is rounded once to out's dtype."""
+    M, R = out.shape[0], B.shape[2]
+    ra = row_adapter[:M].long()
+    cols = slice_of_row.long()[:, None] * R + torch.arange(R)[None, :]  # [N, R]: the columns of t row n reads
+    for a in sorted(set(ra.tolist()) - {-1}):
+        rows = (ra == a).nonzero().flatten()
+        d = (t[rows].float()[:, cols] * B[a].float()[None]).sum(-1) * float(scale[a])
+        out[rows] = (out[rows].float() + d).to(out.dtype)

@@ -37,6 +37,21 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
 
     cfg.validate()  # option combinations (quantization with tp > 1, ...) fail here, before any weight is loaded
     quant = cfg.quantization
+
+    def lora_pool(mcfg, dev):
+        """--enable-lora: every --lora-modules entry loaded into the device pool (None with LoRA off).  A refused
+        adapter (rank above --max-lora-rank, DoRA, a foreign shape, ...) is a start-up error that names its file."""
+        if not cfg.enable_lora:
+            return None
+        from ..engine.lora import build_pool
+        from .config import parse_lora_modules
+
+        pool = build_pool(mcfg, parse_lora_modules(cfg.lora_modules), cfg.max_loras, cfg.max_lora_rank, dev)
+        if comm is None or comm.rank == 0:
+            print(f"[engine] LoRA: {pool.slots} slots of rank {pool.R} ({pool.nbytes() / 1e6:.1f} MB), adapters "
+                  f"{[n for n in pool.names if n is not None]}", flush=True)
+        return pool
+
     if cfg.engine == "cpu":
         mcfg = TINY if cfg.model.startswith("mistral-7b") else get_config(cfg.model)
         tp_rank, tp = (comm.rank, comm.size) if comm is not None else (0, 1)
@@ -44,7 +59,7 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
                              quantization=quant)
         runner = ModelRunner(w, num_blocks=256, max_batch=min(cfg.max_batch, 8),
                              max_model_len=min(cfg.max_model_len, 1024), device="cpu", comm=comm, use_graphs=False,
-                             kv_cache_dtype=cfg.kv_cache_dtype)
+                             kv_cache_dtype=cfg.kv_cache_dtype, lora=lora_pool(mcfg, "cpu"))
     else:
         device = device or torch.device("cuda", torch.cuda.current_device())
         mcfg = get_config(cfg.model)
@@ -54,6 +69,7 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         else:
             w = random_engine_weights(mcfg, tp_rank=tp_rank, tp_size=tp, device=device, seed=cfg.seed,
                                       quantization=quant)
+        pool = lora_pool(mcfg, device)  # resident before the page budget below is sized, so its bytes are counted
         # the page budget below is what is free once the weights are resident: under quantization both copies (the
         # widened bf16 one, 14.5 GB for Mistral-7B, and the FP8 one, 7.2 GB) are already allocated here
         free, total = torch.cuda.mem_get_info(device)
@@ -62,7 +78,7 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         nblk = max(64, min(KVCache.blocks_for_budget(budget, mcfg.num_layers, nkv, kv_cache_torch_dtype(cfg.kv_cache_dtype)),
                            cfg.max_batch * (cfg.max_model_len // 32 + 2) * 4))
         runner = ModelRunner(w, num_blocks=nblk, max_batch=cfg.max_batch, max_model_len=cfg.max_model_len,
-                             device=device, comm=comm, kv_cache_dtype=cfg.kv_cache_dtype)
+                             device=device, comm=comm, kv_cache_dtype=cfg.kv_cache_dtype, lora=pool)
         runner.capture()
     kv = runner.kv
     if comm is None or comm.rank == 0:
@@ -183,7 +199,8 @@ class EngineLoop(threading.Thread):
             # guided_regex, or guided_choice lowered to a pattern (compiled once by the HTTP server to validate it)
             guide=req.get("guide") or None,
             guide_schema=bool(req.get("guide_schema")),  # guided_json / response_format json_schema, lowered
-            json_object=bool(req.get("guide_json")))  # response_format {"type": "json_object"}
+            json_object=bool(req.get("guide_json")),  # response_format {"type": "json_object"}
+            lora=req.get("lora") or None)  # the adapter "model" named (checked against the loaded names by the server)
 
     @staticmethod
     def choice_ids(req) -> list:

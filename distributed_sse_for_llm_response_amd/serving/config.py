@@ -12,7 +12,9 @@ Engine keys (new): TP, DP, DP_PREFIX, DP_WORKER_TIMEOUT_MS, MAX_MODEL_LEN, MAX_B
   SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH, ENABLE_PREFIX_CACHING (default 0),
   DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured), KV_CACHE_DTYPE (auto | bf16 | fp8 | fp8_e4m3; default auto = bf16),
   KV_OFFLOAD_GB (GiB of pinned host memory per engine process behind the prefix cache; default 0 = off),
-  QUANTIZATION (none | fp8; default none; fp8 = FP8 e4m3 weights for decode buckets of 64 rows or fewer, TP = 1).
+  QUANTIZATION (none | fp8; default none; fp8 = FP8 e4m3 weights for decode buckets of 64 rows or fewer, TP = 1),
+  ENABLE_LORA (default 0), LORA_MODULES (comma-separated NAME=PATH of PEFT directories), MAX_LORAS (slots, default 4,
+  at most 8), MAX_LORA_RANK (8 | 16 | 32 | 64, default 16); TP = 1 and bf16 weights only.
 """
 from __future__ import annotations
 
@@ -43,6 +45,28 @@ def parse_quantization(v) -> str:
     if key not in QUANTIZATIONS:
         raise ValueError(f"quantization / QUANTIZATION must be one of {', '.join(QUANTIZATIONS)}; got {v!r}")
     return key
+
+
+# LoRA pool limits (engine/lora.py and ops keep their own copies: no torch import at parse time)
+LORA_RANKS = (8, 16, 32, 64)
+LORA_MAX_SLOTS = 8
+
+
+def parse_lora_modules(v) -> dict:
+    """"NAME=PATH,NAME=PATH" (or a list of NAME=PATH) -> {name: path} in order; a malformed or repeated entry is a
+    start-up error."""
+    items = [s.strip() for s in v.split(",")] if isinstance(v, str) else [str(s).strip() for s in (v or ())]
+    out = {}
+    for it in items:
+        if not it:
+            continue
+        name, sep, path = it.partition("=")
+        if not sep or not name or not path:
+            raise ValueError(f"--lora-modules / LORA_MODULES entries are NAME=PATH; got {it!r}")
+        if name in out:
+            raise ValueError(f"--lora-modules / LORA_MODULES names adapter {name!r} twice")
+        out[name] = path
+    return out
 
 
 def _env(name, default, cast=str):
@@ -110,6 +134,13 @@ class ServeConfig:
     # weight quantisation at load: none, or fp8 = W8A16 e4m3 weights for decode buckets of 64 rows or fewer beside a
     # widened bf16 copy for everything else (not available with tp > 1); passed to every engine replica
     quantization: str = "none"
+    # LoRA serving (engine/lora.py): every NAME=PATH of lora_modules (comma-separated) is loaded into one of max_loras
+    # pool slots of rank max_lora_rank at start-up; "model": NAME of a chat request then selects it.  TP = 1, bf16
+    # weights; passed to every engine replica
+    enable_lora: bool = False
+    lora_modules: str = ""
+    max_loras: int = 4
+    max_lora_rank: int = 16
 
     @classmethod
     def from_env(cls) -> "ServeConfig":
@@ -157,6 +188,10 @@ class ServeConfig:
         c.kv_cache_dtype = _env("KV_CACHE_DTYPE", c.kv_cache_dtype, parse_kv_cache_dtype)
         c.kv_offload_gb = _env("KV_OFFLOAD_GB", c.kv_offload_gb, float)
         c.quantization = _env("QUANTIZATION", c.quantization, parse_quantization)
+        c.enable_lora = _env("ENABLE_LORA", c.enable_lora, bool)
+        c.lora_modules = _env("LORA_MODULES", c.lora_modules)
+        c.max_loras = _env("MAX_LORAS", c.max_loras, int)
+        c.max_lora_rank = _env("MAX_LORA_RANK", c.max_lora_rank, int)
         return c
 
     @classmethod
@@ -171,6 +206,9 @@ class ServeConfig:
             if f.name == "quantization":
                 ap.add_argument("--quantization", type=str.lower, choices=QUANTIZATIONS, default=None)
                 continue
+            if f.name == "lora_modules":  # --lora-modules a=/path/a b=/path/b
+                ap.add_argument("--lora-modules", nargs="+", metavar="NAME=PATH", default=None)
+                continue
             ap.add_argument("--" + f.name.replace("_", "-"), type=type(f.default) if f.default is not None else str,
                             default=None)
 
@@ -178,7 +216,7 @@ class ServeConfig:
         for f in fields(self):
             v = getattr(ns, f.name, None)
             if v is not None:
-                setattr(self, f.name, v)
+                setattr(self, f.name, ",".join(v) if f.name == "lora_modules" and not isinstance(v, str) else v)
         self.kv_cache_dtype = parse_kv_cache_dtype(self.kv_cache_dtype)
         self.quantization = parse_quantization(self.quantization)
         return self.validate()
@@ -200,7 +238,31 @@ class ServeConfig:
             raise ValueError(f"--quantization {self.quantization} / QUANTIZATION is not supported with tensor "
                              f"parallelism (tp = {self.tp}): the row scales are not sharded; run with --tp 1 (data "
                              "parallelism, --dp N, works), or set it to none")
+        mods = parse_lora_modules(self.lora_modules)
+        if mods and not self.enable_lora:
+            raise ValueError("--lora-modules / LORA_MODULES needs --enable-lora (ENABLE_LORA=1)")
+        if self.enable_lora:
+            if self.tp > 1:
+                raise ValueError(f"--enable-lora / ENABLE_LORA is not supported with tensor parallelism (tp = {self.tp}): "
+                                 "the adapters are not sharded; run with --tp 1 (data parallelism, --dp N, works)")
+            if parse_quantization(self.quantization) != "none":
+                raise ValueError(f"--enable-lora / ENABLE_LORA is not supported with --quantization "
+                                 f"{self.quantization}: the FP8 decode kernels cannot take a delta; set it to none")
+            if not 1 <= int(self.max_loras) <= LORA_MAX_SLOTS:
+                raise ValueError(f"--max-loras / MAX_LORAS must be in [1, {LORA_MAX_SLOTS}], got {self.max_loras}")
+            if int(self.max_lora_rank) not in LORA_RANKS:
+                raise ValueError(f"--max-lora-rank / MAX_LORA_RANK must be one of {', '.join(map(str, LORA_RANKS))}, "
+                                 f"got {self.max_lora_rank}")
+            if len(mods) > int(self.max_loras):
+                raise ValueError(f"{len(mods)} --lora-modules for --max-loras {self.max_loras} slots: every adapter is "
+                                 f"loaded at start-up (no eviction); raise --max-loras (at most {LORA_MAX_SLOTS})")
+            if self.model_name in mods:
+                raise ValueError(f"--lora-modules names an adapter {self.model_name!r}, the served model's own name")
         return self
+
+    def lora_names(self) -> list:
+        """The adapters' names, in slot order ([] with LoRA off)."""
+        return list(parse_lora_modules(self.lora_modules)) if self.enable_lora else []
 
     def to_json(self) -> str:
         import json
@@ -224,6 +286,8 @@ class ServeConfig:
         # engine is built with min(MAX_BATCH, 8): serving/app.py build_engine)
         slots = min(self.max_batch, 8) if self.engine == "cpu" else self.max_batch
         out["max_choices"] = max(1, min(16, int(slots)))
+        out["enable_lora"] = bool(self.enable_lora)
+        out["lora_names"] = self.lora_names()
         if self.ui_path != "none":
             from pathlib import Path
 

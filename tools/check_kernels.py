@@ -95,6 +95,34 @@ def check_w8(dev):
         ops.refresh_env()
 
 
+def check_lora(dev):
+    """The multi-LoRA products (lora.hip): the row counts and ranks of tests/test_lora_gpu.py must record nothing; an
+    adapter slot past the pool must be caught in that file (the row is then treated as having no adapter)."""
+    g = torch.Generator().manual_seed(9)
+    K, N, slots = 1024, 1536, 2
+    ops.kernel_checks()  # clear
+    for R in (8, 16, 32, 64):
+        for S in (1, 2, 3):
+            A = (torch.randn(slots, S * R, K, generator=g) / 32).bfloat16().to(dev)
+            B = torch.randn(slots, N, R, generator=g).bfloat16().to(dev)
+            sl = (torch.arange(N) * S // N).int().to(dev)
+            scale = torch.ones(slots, device=dev)
+            for M in (1, 16, 17, 65, 300):
+                x = torch.randn(M, K, generator=g).bfloat16().to(dev)
+                ra = (torch.arange(M) % (slots + 1) - 1).int().to(dev)
+                t = torch.empty(M, S * R, device=dev)
+                ops.lora_shrink(x, A, ra, t)
+                for dt in (torch.float32, torch.bfloat16):
+                    ops.lora_expand_add(t, B, scale, ra, sl, torch.zeros(M, N, device=dev, dtype=dt))
+    clean = ops.kernel_checks(raise_on_error=False)
+    if clean:
+        raise SystemExit(f"false positive on valid LoRA launches: {clean}")
+    print("lora.hip: clean over the ranks, slice counts and row counts")
+    bad = ra.clone()
+    bad[0] = slots + 3
+    expect(lambda: ops.lora_shrink(x, A, bad, t), "lora.hip", "LoRA shrink: adapter slot past the pool")
+
+
 def main():
     dev = torch.device("cuda", 0)
     ops.load_library(required=True)
@@ -102,6 +130,12 @@ def main():
         raise SystemExit("not the checked build: set DSSE_KERNELS_VARIANT=checked")
     if sys.argv[1:] == ["--only", "w8"]:
         check_w8(dev)
+        torch.cuda.synchronize()
+        print("CHECKS-OK")
+        return
+
+    if sys.argv[1:] == ["--only", "lora"]:
+        check_lora(dev)
         torch.cuda.synchronize()
         print("CHECKS-OK")
         return
@@ -168,6 +202,7 @@ def main():
     expect(lambda: ops.decode_prep(act, torch.tensor([70], **i32), bt, torch.zeros(1, **i32), torch.zeros(1, **i32),
                                    torch.zeros(1, **i32), nblk), "elementwise.hip", "decode_prep: bad page id")
     check_w8(dev)
+    check_lora(dev)
     torch.cuda.synchronize()
     print("CHECKS-OK")
 
