@@ -23,6 +23,19 @@ constexpr int kTileChunk = 16 * 128;  // elements per (tile, chunk) block
 // (the same k = 32g + 8s + j as the bf16 layout).  A wave loads every block as two fully contiguous 1 KiB runs.
 constexpr int kTileChunkF8 = 16 * 128;  // bytes per (tile, chunk) block
 
+// MXFP4 weights (gemm_w4.hip; ops/reference.py quantize_weight_mxfp4 / tile_weight_mxfp4): OCP e2m1 elements with one
+// e8m0 scale byte per 32 consecutive K, value = e2m1(nibble) * 2^(scale byte - 127), exact in bf16.  Nibble code: bit 3
+// sign, bits 2-1 exponent, bit 0 mantissa ({0, 0.5, 1, 1.5, 2, 3, 4, 6}; a zero is always code 0); a byte holds element
+// k (even) in its low nibble and element k + 1 in its high nibble.  Device layout, two tensors over the same
+// (16-row tile T, 128-column K-chunk c) blocks, block-major (T, c):
+//   Wq [N, K / 2] bytes, 1 KiB per block: [lane = 0..63][b = 0..15] where lane l = r + 16g holds the 16 contiguous
+//     bytes of W[16T + r][128c + 32g .. 32g + 31] -- one MX block; dword t of them widens to the MFMA B-operand
+//     fragment of k-step t (k = 32g + 8t + j).  A wave loads every block as one contiguous 1 KiB run.
+//   E  [N, K / 32] bytes, 64 B per block: byte [lane] is the scale of that lane's MX block, W's row 16T + r, columns
+//     128c + 32g .. 32g + 31.  A wave's scales over its K range are one contiguous run.
+constexpr int kTileChunkF4 = 16 * 128 / 2;  // nibble bytes per (tile, chunk) block
+constexpr int kTileScaleF4 = 16 * 128 / 32;  // scale bytes per (tile, chunk) block
+
 struct GemmEpi {
   void* out;          // bf16 / f32 output (modes 0, 1, 3)
   int ldo;
@@ -244,6 +257,8 @@ hipError_t dsse_gemm_ring(int mode, int nw, int S, int partial_only, int ring2, 
                           const void* W, int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
 hipError_t dsse_gemm_w8(int mode, int nw, int S, int partial_only, const void* X, int ldx, int M, const void* W,
                         const float* scale, int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
+hipError_t dsse_gemm_w4(int mode, int nw, int S, int partial_only, const void* X, int ldx, int M, const void* W,
+                        const void* E, int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
 hipError_t dsse_gemm_wide(int mode, int mb, int rd, int S, int partial_only, const void* X, int ldx, int M, const void* W,
                           int K, int N, const dsse::GemmEpi* ep, float* part, hipStream_t st);
 hipError_t dsse_gemm_tiled(int mode, int cfg, int S, int partial_only, const void* X, int ldx, int M, const void* W,
@@ -324,6 +339,7 @@ hipError_t dsse_check_sampler(int* out, int clear);
 hipError_t dsse_check_gemm_tiled(int* out, int clear);
 hipError_t dsse_check_kv_pages(int* out, int clear);
 hipError_t dsse_check_gemm_w8(int* out, int clear);
+hipError_t dsse_check_gemm_w4(int* out, int clear);
 hipError_t dsse_check_lora(int* out, int clear);
 // Stamps build: bind the step-anatomy record buffer (common.h stamps::) of a kernel file; no-ops otherwise.
 hipError_t dsse_stamps_bind_gemm_stream(void* rec);

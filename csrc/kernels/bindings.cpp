@@ -46,7 +46,7 @@ void check_dtype(const Tensor& t, at::ScalarType st, const char* name) {
 // Kernel-configuration overrides: ONE environment variable, DSSE_KERNEL_CFG = "key=value,key=value" (diagnostics and
 // the tests that force a kernel path; e.g. "gemm_impl=4,t_cfg=8,t_split=2").  Keys name the selector inputs below
 // (gemm_impl, t_cfg, t_split, t_small, s_nw, s_nt, s_rd, s_split, s_ring, ring2, resid_nw, resid_split, qkv_split, w_split, w_rd,
-// gemm_nt, gemm_kw, attn_kwv, attn_pd, fused_qkv_attn, trap_fpe, w8_nw, w8_split); docs/operations.md lists them.  Parsed once per
+// gemm_nt, gemm_kw, attn_kwv, attn_pd, fused_qkv_attn, trap_fpe, w8_nw, w8_split, w4_nw, w4_split); docs/operations.md lists them.  Parsed once per
 // thread into a thread-local map: no getenv and no lock on the launch path.  refresh_env() (op dsse::refresh_env, for
 // the tools that change it in-process) bumps a generation that makes every thread re-parse on its next lookup.
 std::atomic<uint64_t> g_env_gen{1};
@@ -748,6 +748,131 @@ void gemm_silu_w8(const Tensor& x, const Tensor& wq, const Tensor& ws, Tensor& o
   run_gemm_w8(dsse::kSiluMul, x, wq, ws, ep);
 }
 
+// ---- MXFP4-weight decode GEMMs (gemm_w4.hip): x bf16 [M <= 64, K], w_q nibble bytes [N, K / 2] in the kTileChunkF4
+// layout, w_e e8m0 scale bytes [N, K / 32] in the kTileScaleF4 layout.  One kernel family for every row count.  (waves
+// per workgroup, K split): a workgroup stages the X image of a chunk (16 KiB at 64 rows) once for all its waves and
+// each wave adds 1088 B of weight, so unlike pick_w8 the choice minimises the bytes a CU moves through its LDS-DMA
+// path -- rounds of 256 workgroups x chunks per workgroup x (X image + waves x 1088 B), plus the slab traffic of a
+// split (each wave writes 4 KiB at 64 rows that a consumer reads back); ties go to the most waves, then the smallest
+// split (qkv 6 x 4, o / down 8 x 8, gate_up 7 x 1, LM head 8 x 1 at the Mistral-7B shapes).  The model is arithmetic at
+// 64 rows, not a fit to measurements.  DSSE_KERNEL_CFG overrides: w4_nw, w4_split.
+struct W4Cfg {
+  int nw, S;
+};
+W4Cfg pick_w4(int N, int K) {
+  const int tiles = N / 16, chunks = K / 128;
+  const int e_nw = env_int("w4_nw", 0), e_s = env_int("w4_split", 0);
+  W4Cfg best{0, 1};
+  int64_t best_c = -1;
+  for (int nw : {8, 7, 6, 4, 3}) {
+    if (tiles % nw != 0 || (e_nw > 0 && nw != e_nw)) continue;
+    for (int S : {1, 2, 4, 8}) {
+      if (chunks % S != 0 || (e_s > 0 && S != e_s)) continue;
+      const int64_t total = (int64_t)tiles / nw * S, rounds = (total + 255) / 256;
+      const int64_t c = rounds * ((int64_t)chunks / S * (16384 + nw * 1088) + (S > 1 ? nw * 8192 : 0));
+      if (best_c < 0 || c < best_c) {  // ties: the earlier candidate (more waves, then the smaller split)
+        best = {nw, S};
+        best_c = c;
+      }
+    }
+  }
+  return best;
+}
+
+void check_w4(const Tensor& x, const Tensor& wq, const Tensor& we, int& M, int& N, int& K) {
+  check_gpu(x, "x");
+  check_gpu(wq, "w_q");
+  check_gpu(we, "w_e");
+  check_dtype(x, at::kBFloat16, "x");
+  check_dtype(wq, at::kByte, "w_q");
+  check_dtype(we, at::kByte, "w_e");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && we.dim() == 2, "x, w_q and w_e must be 2-D");
+  M = (int)x.size(0);
+  K = (int)x.size(1);
+  N = (int)wq.size(0);
+  TORCH_CHECK(wq.size(1) * 2 == K, "K mismatch: x ", K, " vs w_q ", wq.size(1), " bytes of two nibbles");
+  TORCH_CHECK(we.size(0) == N && we.size(1) * 32 == K, "w_e must hold one scale byte per 32 columns of every row [",
+              N, ", ", K / 32, "], got [", we.size(0), ", ", we.size(1), "]");
+  TORCH_CHECK(M >= 1 && M <= 64, "the MXFP4-weight GEMMs cover 1-64 rows, got ", M, " (wider batches use the widened bf16 copy)");
+  TORCH_CHECK(K % 128 == 0, "K must be a multiple of 128, got ", K);
+  TORCH_CHECK(N % 16 == 0, "N must be a multiple of 16, got ", N);
+  TORCH_CHECK((int64_t)N * K < (1LL << 31), "weight larger than 2^31 elements: the decode GEMMs address it with 32-bit offsets");
+}
+
+W4Cfg cfg_w4(int N, int K) {
+  const W4Cfg c = pick_w4(N, K);
+  TORCH_CHECK(c.nw > 0, "no MXFP4-weight GEMM for N=", N, " K=", K, " (N / 16 must be a multiple of 3, 4, 6, 7 or 8 waves)");
+  return c;
+}
+
+void run_gemm_w4(int mode, const Tensor& x, const Tensor& wq, const Tensor& we, dsse::GemmEpi& ep) {
+  int M, N, K;
+  check_w4(x, wq, we, M, N, K);
+  const W4Cfg c = cfg_w4(N, K);
+  at::Tensor part;
+  if (c.S > 1) part = at::empty({(int64_t)c.S * M * N}, x.options().dtype(at::kFloat));
+  DSSE_CHECK_HIP(dsse_gemm_w4(mode, c.nw, c.S, 0, x.data_ptr(), K, M, wq.data_ptr(), we.data_ptr(), K, N, &ep,
+                              c.S > 1 ? part.data_ptr<float>() : nullptr, cur_stream()));
+}
+
+void gemm_out_w4(const Tensor& x, const Tensor& wq, const Tensor& we, Tensor& out) {
+  check_gpu(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == x.size(0) && out.size(1) == wq.size(0), "out must be [M, N]");
+  dsse::GemmEpi ep{};
+  ep.out = out.data_ptr();
+  ep.ldo = (int)out.size(1);
+  int mode;
+  if (out.scalar_type() == at::kBFloat16) mode = dsse::kStoreBf16;
+  else if (out.scalar_type() == at::kFloat) mode = dsse::kStoreF32;
+  else TORCH_CHECK(false, "out must be bf16 or fp32");
+  run_gemm_w4(mode, x, wq, we, ep);
+}
+
+void gemm_resid_w4(const Tensor& x, const Tensor& wq, const Tensor& we, Tensor& resid) {
+  check_gpu(resid, "resid");
+  check_dtype(resid, at::kFloat, "resid");
+  TORCH_CHECK(resid.dim() == 2 && resid.size(0) == x.size(0) && resid.size(1) == wq.size(0), "resid must be [M, N]");
+  dsse::GemmEpi ep{};
+  ep.resid = resid.data_ptr<float>();
+  ep.ldr = (int)resid.size(1);
+  run_gemm_w4(dsse::kResidAdd, x, wq, we, ep);
+}
+
+// The split forms (gemm_resid_split / gemm_out_split): fp32 slabs [S, M, N] into `part` and S returned when the launch
+// splits K and `part` holds them, else the plain op and 0.
+int64_t gemm_split_w4(int mode, const Tensor& x, const Tensor& wq, const Tensor& we, Tensor& part) {
+  int M, N, K;
+  check_w4(x, wq, we, M, N, K);
+  check_gpu(part, "part");
+  check_dtype(part, at::kFloat, "part");
+  const W4Cfg c = cfg_w4(N, K);
+  if (c.S <= 1 || part.numel() < (int64_t)c.S * M * N) return 0;
+  dsse::GemmEpi ep{};
+  DSSE_CHECK_HIP(dsse_gemm_w4(mode, c.nw, c.S, 1, x.data_ptr(), K, M, wq.data_ptr(), we.data_ptr(), K, N, &ep,
+                              part.data_ptr<float>(), cur_stream()));
+  return c.S;
+}
+int64_t gemm_resid_split_w4(const Tensor& x, const Tensor& wq, const Tensor& we, Tensor& resid, Tensor& part) {
+  const int64_t S = gemm_split_w4(dsse::kResidAdd, x, wq, we, part);
+  if (S == 0) gemm_resid_w4(x, wq, we, resid);
+  return S;
+}
+int64_t gemm_out_split_w4(const Tensor& x, const Tensor& wq, const Tensor& we, Tensor& out, Tensor& part) {
+  const int64_t S = gemm_split_w4(dsse::kStoreBf16, x, wq, we, part);
+  if (S == 0) gemm_out_w4(x, wq, we, out);
+  return S;
+}
+
+void gemm_silu_w4(const Tensor& x, const Tensor& wq, const Tensor& we, Tensor& out) {
+  check_gpu(out, "out");
+  check_dtype(out, at::kBFloat16, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == x.size(0) && out.size(1) * 2 == wq.size(0), "out must be [M, N/2]");
+  dsse::GemmEpi ep{};
+  ep.out = out.data_ptr();
+  ep.ldo = (int)out.size(1);
+  run_gemm_w4(dsse::kSiluMul, x, wq, we, ep);
+}
+
 // The KV cache element type of an op call: bf16 (false) or FP8 e4m3fn (true); both caches must agree, and anything
 // else is refused -- no kernel reads a cache dtype it was not instantiated for.  Scales must be positive and finite.
 bool cache_is_f8(const Tensor& k_cache, const Tensor& v_cache, double k_scale, double v_scale) {
@@ -764,9 +889,11 @@ bool cache_is_f8(const Tensor& k_cache, const Tensor& v_cache, double k_scale, d
 }
 
 // ws: the row scales of an FP8 weight (w then holds its bytes and the projection runs on gemm_w8.hip), or null.
+// we: the block scale bytes of an MXFP4 weight (w then holds its nibbles: gemm_w4.hip), or null.  At most one is set.
 void gemm_qkv_rope_impl(const Tensor& x, const Tensor& w, const Tensor* ws, const Tensor& positions, const Tensor& slots,
                         const Tensor& rope, Tensor& q_out, Tensor& k_cache, Tensor& v_cache, int64_t nh,
-                        int64_t nkv, double k_scale, double v_scale, const c10::optional<Tensor>& scratch) {
+                        int64_t nkv, double k_scale, double v_scale, const c10::optional<Tensor>& scratch,
+                        const Tensor* we = nullptr) {
   const bool f8 = cache_is_f8(k_cache, v_cache, k_scale, v_scale);
   for (auto* t : {&positions, &slots, &rope}) check_gpu(*t, "metadata");
   check_gpu(q_out, "q_out");
@@ -815,14 +942,16 @@ void gemm_qkv_rope_impl(const Tensor& x, const Tensor& w, const Tensor* ws, cons
     dsse::GemmEpi ey{};
     ey.out = y.data_ptr();
     ey.ldo = N;
-    if (ws) run_gemm_w8(dsse::kStoreF32, x, w, *ws, ey);
+    if (we) run_gemm_w4(dsse::kStoreF32, x, w, *we, ey);
+    else if (ws) run_gemm_w8(dsse::kStoreF32, x, w, *ws, ey);
     else run_gemm(dsse::kStoreF32, x, w, ey);
     DSSE_CHECK_HIP(dsse_qkv_rope_f8(M, y.data_ptr<float>(), (int)nh, (int)nkv, ep.positions, ep.slots, ep.rope,
                                     q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), ep.num_slots,
                                     ep.rope_len, (float)(1.0 / k_scale), (float)(1.0 / v_scale), cur_stream()));
     return;
   }
-  if (ws) run_gemm_w8(dsse::kQkvRope, x, w, *ws, ep);
+  if (we) run_gemm_w4(dsse::kQkvRope, x, w, *we, ep);
+  else if (ws) run_gemm_w8(dsse::kQkvRope, x, w, *ws, ep);
   else run_gemm(dsse::kQkvRope, x, w, ep);
 }
 
@@ -835,6 +964,12 @@ void gemm_qkv_rope_w8(const Tensor& x, const Tensor& wq, const Tensor& ws, const
                       const Tensor& rope, Tensor& q_out, Tensor& k_cache, Tensor& v_cache, int64_t nh, int64_t nkv,
                       double k_scale, double v_scale, const c10::optional<Tensor>& scratch) {
   gemm_qkv_rope_impl(x, wq, &ws, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale, scratch);
+}
+void gemm_qkv_rope_w4(const Tensor& x, const Tensor& wq, const Tensor& we, const Tensor& positions, const Tensor& slots,
+                      const Tensor& rope, Tensor& q_out, Tensor& k_cache, Tensor& v_cache, int64_t nh, int64_t nkv,
+                      double k_scale, double v_scale, const c10::optional<Tensor>& scratch) {
+  gemm_qkv_rope_impl(x, wq, nullptr, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale,
+                     scratch, &we);
 }
 
 void rmsnorm(Tensor& resid, const Tensor& w, Tensor& y, double eps, const c10::optional<Tensor>& delta,
@@ -1095,18 +1230,25 @@ int64_t qkv_attention_decode_impl(const Tensor& x, const Tensor& w, const Tensor
                              int64_t nkv, Tensor& slabs, const Tensor& block_tables, const Tensor& q_start,
                              const Tensor& q_len, const Tensor& ctx_len, const Tensor& work_seq,
                              const Tensor& work_tile, Tensor& out, Tensor& part_o, Tensor& part_ml, int64_t part,
-                             int64_t nparts, double k_scale, double v_scale) {
+                             int64_t nparts, double k_scale, double v_scale, const Tensor* we = nullptr) {
   check_gpu(x, "x");
   check_gpu(w, "w");
   check_gpu(slabs, "slabs");
   check_dtype(slabs, at::kFloat, "slabs");
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
-  const bool shape_ok = x.dim() == 2 && w.dim() == 2 && M >= 1 && K % 128 == 0 && w.size(1) == K &&
-                        N == (nh + 2 * nkv) * 128;
-  const int impl = (shape_ok && !ws) ? gemm_impl(M, N, K) : 0;
+  const bool shape_ok = x.dim() == 2 && w.dim() == 2 && M >= 1 && K % 128 == 0 &&
+                        w.size(1) * (we ? 2 : 1) == K && N == (nh + 2 * nkv) * 128;
+  const int impl = (shape_ok && !ws && !we) ? gemm_impl(M, N, K) : 0;
   int S = 0;
   W8Cfg c8{0, 1};
-  if (ws) {  // FP8 weight: every row count leaves (scaled) slabs, one slab when the launch does not split K
+  W4Cfg c4{0, 1};
+  if (we) {  // MXFP4 weight: as the FP8 one, every row count leaves slabs
+    int m_, n_, k_;
+    check_w4(x, w, *we, m_, n_, k_);
+    TORCH_CHECK(shape_ok, "w_q rows must be (nh + 2 nkv) * 128");
+    c4 = cfg_w4(N, K);
+    S = c4.S;
+  } else if (ws) {  // FP8 weight: every row count leaves (scaled) slabs, one slab when the launch does not split K
     int m_, n_, k_;
     check_w8(x, w, *ws, m_, n_, k_);
     TORCH_CHECK(shape_ok, "w_q rows must be (nh + 2 nkv) * 128");
@@ -1128,13 +1270,13 @@ int64_t qkv_attention_decode_impl(const Tensor& x, const Tensor& w, const Tensor
   auto o3 = out.view({-1, nh, 128});
   const bool group_ok = nkv > 0 && nh % nkv == 0 && (nh / nkv == 1 || nh / nkv == 2 || nh / nkv == 4);  // attention.hip
   if ((S <= 0 || !group_ok || slabs.numel() < (int64_t)S * M * N || env_int("fused_qkv_attn", 1) == 0)) {
-    gemm_qkv_rope_impl(x, w, ws, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale, slabs);
+    gemm_qkv_rope_impl(x, w, ws, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale, slabs, we);
     paged_attention(0, q3, k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq, work_tile, o3, part_o,
                     part_ml, part, nparts, k_scale, v_scale);
     return 0;
   }
   check_dtype(x, at::kBFloat16, "x");
-  if (!ws) check_dtype(w, at::kBFloat16, "w");
+  if (!ws && !we) check_dtype(w, at::kBFloat16, "w");
   for (auto* t : {&positions, &slots}) {
     check_gpu(*t, "metadata");
     check_dtype(*t, at::kInt, "metadata");
@@ -1150,7 +1292,10 @@ int64_t qkv_attention_decode_impl(const Tensor& x, const Tensor& w, const Tensor
   dsse::GemmEpi ep{};
   const void* X = x.data_ptr();
   float* sl = slabs.data_ptr<float>();
-  if (ws) {
+  if (we) {
+    DSSE_CHECK_HIP(dsse_gemm_w4(dsse::kQkvRope, c4.nw, S, 1, X, K, M, w.data_ptr(), we->data_ptr(), K, N, &ep, sl,
+                                cur_stream()));
+  } else if (ws) {
     DSSE_CHECK_HIP(dsse_gemm_w8(dsse::kQkvRope, c8.nw, S, 1, X, K, M, w.data_ptr(), ws->data_ptr<float>(), K, N, &ep, sl,
                                 cur_stream()));
   } else if (impl == 4) {
@@ -1197,6 +1342,16 @@ int64_t qkv_attention_decode_w8(const Tensor& x, const Tensor& wq, const Tensor&
   return qkv_attention_decode_impl(x, wq, &ws, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, slabs,
                                    block_tables, q_start, q_len, ctx_len, work_seq, work_tile, out, part_o, part_ml, part,
                                    nparts, k_scale, v_scale);
+}
+int64_t qkv_attention_decode_w4(const Tensor& x, const Tensor& wq, const Tensor& we, const Tensor& positions,
+                                const Tensor& slots, const Tensor& rope, Tensor& q_out, Tensor& k_cache, Tensor& v_cache,
+                                int64_t nh, int64_t nkv, Tensor& slabs, const Tensor& block_tables, const Tensor& q_start,
+                                const Tensor& q_len, const Tensor& ctx_len, const Tensor& work_seq,
+                                const Tensor& work_tile, Tensor& out, Tensor& part_o, Tensor& part_ml, int64_t part,
+                                int64_t nparts, double k_scale, double v_scale) {
+  return qkv_attention_decode_impl(x, wq, nullptr, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, slabs,
+                                   block_tables, q_start, q_len, ctx_len, work_seq, work_tile, out, part_o, part_ml, part,
+                                   nparts, k_scale, v_scale, &we);
 }
 
 // ---- operand checks shared by the sampler ops ------------------------------------------------------------------
@@ -1922,6 +2077,12 @@ std::tuple<int64_t, int64_t> gemm_w8_plan(int64_t N, int64_t K) {
   const W8Cfg c = pick_w8((int)N, (int)K);
   return {c.nw, c.S};
 }
+// Likewise the MXFP4-weight dispatch's.
+std::tuple<int64_t, int64_t> gemm_w4_plan(int64_t N, int64_t K) {
+  if (N < 16 || K < 128 || N % 16 != 0 || K % 128 != 0) return {0, 0};
+  const W4Cfg c = pick_w4((int)N, (int)K);
+  return {c.nw, c.S};
+}
 
 // Stamps build: the last fix-up launch's per-workgroup phase stamps ([kStampWgs, 8] int64; empty otherwise).
 at::Tensor gemm_fix_stamps(int64_t device) {
@@ -1944,21 +2105,21 @@ bool kernels_checked() { return true; }
 bool kernels_checked() { return false; }
 #endif
 
-// Checked build: [10, 4] int32 (line, value, bound, count) of the first out-of-range index per kernel file,
+// Checked build: [11, 4] int32 (line, value, bound, count) of the first out-of-range index per kernel file,
 // in the order of kCheckFiles; all zeros in the default build.  Synchronises the device.
-const char* const kCheckFiles[10] = {"gemm_skinny.hip", "gemm_stream.hip", "attention.hip", "attention_prefill.hip",
+const char* const kCheckFiles[11] = {"gemm_skinny.hip", "gemm_stream.hip", "attention.hip", "attention_prefill.hip",
                                     "elementwise.hip", "sampler.hip", "gemm_tiled.hip", "kv_pages.hip",
-                                    "gemm_w8.hip", "lora.hip"};
+                                    "gemm_w8.hip", "lora.hip", "gemm_w4.hip"};
 Tensor kernel_checks(bool clear) {
   using Reader = hipError_t (*)(int*, int);
-  static const Reader readers[10] = {dsse_check_gemm_skinny, dsse_check_gemm_stream, dsse_check_attention,
+  static const Reader readers[11] = {dsse_check_gemm_skinny, dsse_check_gemm_stream, dsse_check_attention,
                                     dsse_check_attention_prefill, dsse_check_elementwise, dsse_check_sampler,
                                     dsse_check_gemm_tiled, dsse_check_kv_pages, dsse_check_gemm_w8,
-                                     dsse_check_lora};
-  Tensor out = at::zeros({10, 4}, at::kInt);
+                                     dsse_check_lora, dsse_check_gemm_w4};
+  Tensor out = at::zeros({11, 4}, at::kInt);
   if (!kernels_checked()) return out;
   DSSE_CHECK_HIP(hipDeviceSynchronize());
-  for (int i = 0; i < 10; ++i) DSSE_CHECK_HIP(readers[i](out.data_ptr<int>() + 4 * i, clear ? 1 : 0));
+  for (int i = 0; i < 11; ++i) DSSE_CHECK_HIP(readers[i](out.data_ptr<int>() + 4 * i, clear ? 1 : 0));
   return out;
 }
 // Stamps build: step-anatomy records (common.h stamps::record) of the ring GEMMs and RMSNorms.  step_stamps_arm
@@ -2057,6 +2218,21 @@ TORCH_LIBRARY(dsse, m) {
         "Tensor(e!) out, Tensor(f!) part_o, Tensor(g!) part_ml, int part, int nparts, float k_scale=1.0, "
         "float v_scale=1.0) -> int");
   m.def("gemm_w8_plan(int N, int K) -> (int, int)", &gemm_w8_plan);
+  // MXFP4-weight forms (gemm_w4.hip): w_q = e2m1 nibble bytes, w_e = e8m0 block scale bytes, both in the tiled layout
+  m.def("gemm_out_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor(a!) out) -> ()");
+  m.def("gemm_resid_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor(a!) resid) -> ()");
+  m.def("gemm_resid_split_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor(a!) resid, Tensor(b!) part) -> int");
+  m.def("gemm_out_split_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor(a!) out, Tensor(b!) part) -> int");
+  m.def("gemm_silu_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor(a!) out) -> ()");
+  m.def("gemm_qkv_rope_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor positions, Tensor slots, Tensor rope, "
+        "Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv, float k_scale=1.0, "
+        "float v_scale=1.0, Tensor(d!)? scratch=None) -> ()");
+  m.def("qkv_attention_decode_w4(Tensor x, Tensor w_q, Tensor w_e, Tensor positions, Tensor slots, Tensor rope, "
+        "Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, int nh, int nkv, Tensor(d!) slabs, "
+        "Tensor block_tables, Tensor q_start, Tensor q_len, Tensor ctx_len, Tensor work_seq, Tensor work_tile, "
+        "Tensor(e!) out, Tensor(f!) part_o, Tensor(g!) part_ml, int part, int nparts, float k_scale=1.0, "
+        "float v_scale=1.0) -> int");
+  m.def("gemm_w4_plan(int N, int K) -> (int, int)", &gemm_w4_plan);
   m.def("sample_candidates(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, "
         "Tensor positions, Tensor? active, Tensor(a!) cand, int vocab_offset=0) -> ()");
   m.def("sample_pick(Tensor cand_all, Tensor? active, Tensor(a!) next_ids, Tensor(b!)? ring=None, "
@@ -2138,6 +2314,13 @@ TORCH_LIBRARY_IMPL(dsse, CUDA, m) {
   m.impl("gemm_silu_w8", &gemm_silu_w8);
   m.impl("gemm_qkv_rope_w8", &gemm_qkv_rope_w8);
   m.impl("qkv_attention_decode_w8", &qkv_attention_decode_w8);
+  m.impl("gemm_out_w4", &gemm_out_w4);
+  m.impl("gemm_resid_w4", &gemm_resid_w4);
+  m.impl("gemm_resid_split_w4", &gemm_resid_split_w4);
+  m.impl("gemm_out_split_w4", &gemm_out_split_w4);
+  m.impl("gemm_silu_w4", &gemm_silu_w4);
+  m.impl("gemm_qkv_rope_w4", &gemm_qkv_rope_w4);
+  m.impl("qkv_attention_decode_w4", &qkv_attention_decode_w4);
   m.impl("sample_candidates", &sample_candidates);
   m.impl("sample_pick", &sample_pick);
   m.impl("prefill_sample_gather", &prefill_sample_gather);

@@ -108,7 +108,7 @@ def _build_runner(model: str, device, streams: int, prompt_len: int, total_steps
     # benchmark times an fp8 cache without a flag of its own
     if kv_cache_dtype is None:
         kv_cache_dtype = os.environ.get("KV_CACHE_DTYPE") or "auto"
-    # likewise the serving key QUANTIZATION (none | fp8): unset, the weights and every kernel are what they were
+    # likewise the serving key QUANTIZATION (none | fp8 | mxfp4): unset, the weights and every kernel are what they were
     quantization = os.environ.get("QUANTIZATION") or None
     # on CPU the 7B architecture is replaced by the tiny one (plumbing runs); named small configs are kept
     cfg = get_config(model) if device.type == "cuda" or not model.startswith("mistral-7b") else TINY

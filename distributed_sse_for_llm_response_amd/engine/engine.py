@@ -374,7 +374,7 @@ class LLMEngine:
         # the runner's KV cache element type ("bf16" | "fp8_e4m3": ModelRunner(kv_cache_dtype=)); nothing the engine
         # schedules -- pages, block tables, slots, prefix hashes -- depends on it
         self.kv_cache_dtype = "fp8_e4m3" if runner.kv.is_fp8 else "bf16"
-        # the runner's weight quantisation ("none" | "fp8_e4m3": ModelRunner(quantization=)); it changes which GEMM
+        # the runner's weight quantisation ("none" | "fp8_e4m3" | "mxfp4": ModelRunner(quantization=)); it changes which GEMM
         # kernels a decode bucket runs and nothing the engine schedules
         self.quantization = getattr(runner, "quantization", "none")
         self.shared_write_violations = 0  # a step's write slots named a shared page (checked when debug_shared_writes)

@@ -214,13 +214,16 @@ class ModelRunner:
         # quantization "fp8": FP8 (e4m3) weights beside a widened bf16 copy (engine/weights.py).  Decode buckets of
         # W8_MAX_M rows or fewer run every projection and the LM head on the FP8 kernels over *_q; wider buckets,
         # prefill, mixed steps and the first-token head use the existing kernels over the widened *_t -- identical
-        # weight values on both paths.  None = as the weights were loaded.
+        # weight values on both paths.  "mxfp4": the same arrangement with OCP MXFP4 weights (*_q nibbles, *_e block
+        # scale bytes), W4_MAX_M and the MXFP4 kernels.  None = as the weights were loaded.
         if quantization is not None and parse_quantization(quantization) != "none":
             if (comm.size if comm is not None else 1) > 1:
-                raise ValueError("quantization=fp8 is not supported with tensor parallelism (tp > 1)")
+                raise ValueError(f"quantization={parse_quantization(quantization)} is not supported with tensor "
+                                 "parallelism (tp > 1)")
             quantize_engine_weights(w, quantization)
-        self.quantization = "fp8_e4m3" if w.quantization == "fp8" else "none"
+        self.quantization = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4"}.get(w.quantization, "none")
         self.w8 = w.quantization == "fp8"
+        self.w4 = w.quantization == "mxfp4"
         self.w, self.cfg = w, w.cfg
         self.device = torch.device(device)
         self.comm = comm or TPComm()
@@ -231,6 +234,8 @@ class ModelRunner:
                 raise ValueError("LoRA is not supported with tensor parallelism (tp > 1)")
             if self.w8:
                 raise ValueError("LoRA is not supported with quantization=fp8")
+            if self.w4:
+                raise ValueError("LoRA is not supported with quantization=mxfp4")
         self.lora = lora
         self.lora_used = False  # a request ever named an adapter (then the LoRA body is launched / captured)
         self.max_batch = max_batch
@@ -410,6 +415,17 @@ class ModelRunner:
             self._sample_commit(B)
             ops.ring_advance(self.ring_counter)
             return
+        if self.w4 and B <= ops.W4_MAX_M:
+            for li, L in enumerate(w.layers):
+                self._qkv_attention(li, L, B, x, part, nparts)
+                self._resid_proj_w4(self.attn[r], L.wo_q, L.wo_e, resid, L.ffn_norm, x)
+                ops.gemm_silu_w4(x, L.wgu_q, L.wgu_e, self.h[r])
+                w_next = w.layers[li + 1].attn_norm if li + 1 < nl else w.final_norm
+                self._resid_proj_w4(self.h[r], L.wd_q, L.wd_e, resid, w_next, x)
+            ops.gemm_out_w4(x, w.lm_head_q, w.lm_head_e, self.logits[r])
+            self._sample_commit(B)
+            ops.ring_advance(self.ring_counter)
+            return
         for li, L in enumerate(w.layers):
             self._qkv_attention(li, L, B, x, part, nparts)
             self._resid_proj(self.attn[r], L.wo_t, resid, L.ffn_norm, x, self.tmp[r])
@@ -455,6 +471,13 @@ class ModelRunner:
         nh, nkv = self.w.nh, self.w.nkv
         if self.w8 and B <= ops.W8_MAX_M:
             ops.qkv_attention_decode_w8(x, L.wqkv_q, L.wqkv_scale, self.positions[r], self.slots[r], self.rope,
+                                        self.q[r], self.kv.k[li], self.kv.v[li], nh, nkv, self.split_part,
+                                        self.block_tables[r], self.q_start[r], self.q_len[r], self.ctx_len[r],
+                                        self.work_seq[r], self.work_tile[r], self.attn[r], self.part_o, self.part_ml,
+                                        part, nparts, *self._kv_scales(li))
+            return
+        if self.w4 and B <= ops.W4_MAX_M:
+            ops.qkv_attention_decode_w4(x, L.wqkv_q, L.wqkv_e, self.positions[r], self.slots[r], self.rope,
                                         self.q[r], self.kv.k[li], self.kv.v[li], nh, nkv, self.split_part,
                                         self.block_tables[r], self.q_start[r], self.q_len[r], self.ctx_len[r],
                                         self.work_seq[r], self.work_tile[r], self.attn[r], self.part_o, self.part_ml,
@@ -578,6 +601,11 @@ class ModelRunner:
     def _resid_proj_w8(self, a, wq, ws, resid, norm_w, x) -> None:
         """_resid_proj over an FP8 weight (TP = 1): the scaled split-K slabs are reduced inside the norm."""
         ns = ops.gemm_resid_split_w8(a, wq, ws, resid, self.split_part)
+        ops.rmsnorm(resid, norm_w, x, self.cfg.rms_eps, part=self.split_part, nsplit=ns)
+
+    def _resid_proj_w4(self, a, wq, we, resid, norm_w, x) -> None:
+        """_resid_proj over an MXFP4 weight (TP = 1): the split-K slabs are reduced inside the norm."""
+        ns = ops.gemm_resid_split_w4(a, wq, we, resid, self.split_part)
         ops.rmsnorm(resid, norm_w, x, self.cfg.rms_eps, part=self.split_part, nsplit=ns)
 
     def _sample_commit(self, B: int) -> None:

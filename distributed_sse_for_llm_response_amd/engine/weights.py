@@ -23,6 +23,10 @@ Mistral-7B at TP=1, now KV cache).
 index is the engine row): ``*_q`` = e4m3 bytes in the byte tiled layout (:func:`ops.reference.tile_weight_f8`),
 ``*_scale`` = one fp32 power-of-two scale per row, and ``*_t`` = the tiled copy of ``bf16(q) * scale`` (exact), which
 every kernel without an FP8 form keeps using.  Embedding, norms and rope are left alone.
+
+``quantization="mxfp4"`` (TP = 1 only) does the same with OCP MXFP4: ``*_q`` = e2m1 nibble bytes and ``*_e`` = e8m0
+scale bytes, one per 32 consecutive K of an engine row, both in the tiled layout
+(:func:`ops.reference.tile_weight_mxfp4`), and ``*_t`` = the tiled copy of the exactly widened values.
 """
 from __future__ import annotations
 
@@ -32,14 +36,16 @@ from dataclasses import dataclass
 import torch
 
 from ..models.mistral import MistralConfig
-from ..ops.reference import (gate_up_perm, quantize_weight_f8, rotary_perm, tile_weight, tile_weight_f8,
-                             untile_weight, widen_weight_f8)
+from ..ops.reference import (gate_up_perm, quantize_weight_f8, quantize_weight_mxfp4, rotary_perm, tile_weight,
+                             tile_weight_f8, tile_weight_mxfp4, untile_weight, widen_weight_f8, widen_weight_mxfp4)
 
-QUANTIZATIONS = ("none", "fp8")  # weight quantisation at load: none = bf16 only; fp8 = W8A16 e4m3 beside a widened copy
+# weight quantisation at load: none = bf16 only; fp8 = W8A16 e4m3, mxfp4 = W4A16 OCP MXFP4, each beside a widened copy
+QUANTIZATIONS = ("none", "fp8", "mxfp4")
 
 
 def parse_quantization(v) -> str:
-    """None / "" / "none" -> "none"; "fp8" (or "fp8_e4m3") -> "fp8"; anything else is an error naming the choices."""
+    """None / "" / "none" -> "none"; "fp8" (or "fp8_e4m3") -> "fp8"; "mxfp4" -> "mxfp4"; anything else is an error
+    naming the choices."""
     key = "none" if v is None else str(v).strip().lower()
     key = {"": "none", "fp8_e4m3": "fp8"}.get(key, key)
     if key not in QUANTIZATIONS:
@@ -70,6 +76,12 @@ class LayerWeights:
     wgu_scale: torch.Tensor = None
     wd_q: torch.Tensor = None
     wd_scale: torch.Tensor = None
+    # MXFP4 weights (quantization="mxfp4"): *_q = e2m1 nibble bytes, *_e = e8m0 scale bytes per 32 K of an engine row,
+    # both in the tiled layout (tile_weight_mxfp4); *_t is then the tiled widened copy
+    wqkv_e: torch.Tensor = None
+    wo_e: torch.Tensor = None
+    wgu_e: torch.Tensor = None
+    wd_e: torch.Tensor = None
     # per-layer dequantisation scales of an fp8 KV cache (stored = x / scale); 1.0 unless the checkpoint carries
     # vLLM's model.layers.N.self_attn.k_scale / .v_scale.  The same on every TP rank.  Unused with a bf16 cache.
     k_scale: float = 1.0
@@ -88,6 +100,7 @@ class EngineWeights:
     lm_head_t: torch.Tensor = None
     lm_head_q: torch.Tensor = None
     lm_head_scale: torch.Tensor = None
+    lm_head_e: torch.Tensor = None
     quantization: str = "none"
 
     @property
@@ -112,48 +125,65 @@ class EngineWeights:
 
     def nbytes(self) -> int:
         """Bytes of the resident model: the bf16 copy (what a decode step streams, plus the embedding table) and,
-        under quantization, the FP8 copy beside it."""
+        under quantization, the FP8 or MXFP4 copy beside it."""
         n = self.embed.numel() + self.final_norm.numel() + self.lm_head_t.numel()
         for L in self.layers:
             n += sum(t.numel() for t in (L.attn_norm, L.wqkv_t, L.wo_t, L.ffn_norm, L.wgu_t, L.wd_t))
-        return 2 * n + self.nbytes_fp8()
+        return 2 * n + self.nbytes_fp8() + self.nbytes_fp4()
 
     def nbytes_fp8(self) -> int:
-        """Bytes of the FP8 copy (bytes and scales of every quantised matrix); 0 without quantization."""
+        """Bytes of the FP8 copy (bytes and scales of every quantised matrix); 0 unless quantization is fp8."""
+        if self.quantization != "fp8":
+            return 0
         ts = [self.lm_head_q, self.lm_head_scale]
         for L in self.layers:
             ts += [L.wqkv_q, L.wqkv_scale, L.wo_q, L.wo_scale, L.wgu_q, L.wgu_scale, L.wd_q, L.wd_scale]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
+    def nbytes_fp4(self) -> int:
+        """Bytes of the MXFP4 copy (nibble and scale bytes of every quantised matrix); 0 unless quantization is mxfp4."""
+        if self.quantization != "mxfp4":
+            return 0
+        ts = [self.lm_head_q, self.lm_head_e]
+        for L in self.layers:
+            ts += [L.wqkv_q, L.wqkv_e, L.wo_q, L.wo_e, L.wgu_q, L.wgu_e, L.wd_q, L.wd_e]
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
 
 def _tile(m: torch.Tensor, quantization: str):
-    """(tiled bf16, tiled e4m3 bytes, scales) of one engine-layout matrix: quantised per engine row, the bf16 copy
-    widened from the bytes, so both copies hold identical values; (tile_weight(m), None, None) without quantization."""
-    if quantization != "fp8":
-        return tile_weight(m), None, None
-    q, scale = quantize_weight_f8(m)
-    return tile_weight(widen_weight_f8(q, scale).to(m.dtype)), tile_weight_f8(q), scale
+    """(tiled bf16, tiled quantised bytes, fp32 row scales, tiled e8m0 block scale bytes) of one engine-layout matrix.
+    fp8: quantised per engine row (no block scales); mxfp4: per 32 K of an engine row (no row scales).  The bf16 copy
+    is widened from the bytes, so both copies hold identical values.  (tile_weight(m), None, None, None) without
+    quantization."""
+    if quantization == "fp8":
+        q, scale = quantize_weight_f8(m)
+        return tile_weight(widen_weight_f8(q, scale).to(m.dtype)), tile_weight_f8(q), scale, None
+    if quantization == "mxfp4":
+        q, e = quantize_weight_mxfp4(m)
+        qt, et = tile_weight_mxfp4(q, e)
+        return tile_weight(widen_weight_mxfp4(q, e).to(m.dtype)), qt, None, et
+    return tile_weight(m), None, None, None
 
 
 def _tile_layer(L: LayerWeights, quantization: str) -> None:
-    L.wqkv_t, L.wqkv_q, L.wqkv_scale = _tile(L.wqkv, quantization)
-    L.wo_t, L.wo_q, L.wo_scale = _tile(L.wo, quantization)
-    L.wgu_t, L.wgu_q, L.wgu_scale = _tile(L.wgu, quantization)
-    L.wd_t, L.wd_q, L.wd_scale = _tile(L.wd, quantization)
+    L.wqkv_t, L.wqkv_q, L.wqkv_scale, L.wqkv_e = _tile(L.wqkv, quantization)
+    L.wo_t, L.wo_q, L.wo_scale, L.wo_e = _tile(L.wo, quantization)
+    L.wgu_t, L.wgu_q, L.wgu_scale, L.wgu_e = _tile(L.wgu, quantization)
+    L.wd_t, L.wd_q, L.wd_scale, L.wd_e = _tile(L.wd, quantization)
     L.wqkv = L.wo = L.wgu = L.wd = None
 
 
 @torch.no_grad()
 def attach_tiled(w: EngineWeights, quantization=None) -> EngineWeights:
-    """Convert every GEMM weight to the tiled layout and drop the row-major input (idempotent).  quantization="fp8":
-    the matrices (not the embedding, the norms or rope) are quantised here, once, in the engine layout."""
+    """Convert every GEMM weight to the tiled layout and drop the row-major input (idempotent).  quantization="fp8"
+    or "mxfp4": the matrices (not the embedding, the norms or rope) are quantised here, once, in the engine layout."""
     w.quantization = parse_quantization(quantization) if w.quantization == "none" else w.quantization
     for L in w.layers:
         if L.wqkv_t is None:
             _tile_layer(L, w.quantization)
         L.wqkv = L.wo = L.wgu = L.wd = None
     if w.lm_head_t is None:
-        w.lm_head_t, w.lm_head_q, w.lm_head_scale = _tile(w.lm_head, w.quantization)
+        w.lm_head_t, w.lm_head_q, w.lm_head_scale, w.lm_head_e = _tile(w.lm_head, w.quantization)
     w.lm_head = None
     return w
 
@@ -161,15 +191,20 @@ def attach_tiled(w: EngineWeights, quantization=None) -> EngineWeights:
 @torch.no_grad()
 def quantize_engine_weights(w: EngineWeights, quantization="fp8") -> EngineWeights:
     """Quantise engine weights that were loaded without the option (idempotent): each matrix is taken back from its
-    tiled bf16 copy, quantised per engine row, and both copies are stored as the loaders would have."""
+    tiled bf16 copy, quantised in the engine layout, and both copies are stored as the loaders would have.  Weights
+    already quantised in the other format are refused: their bf16 copy holds rounded values, and quantising those
+    again would silently serve a model rounded twice."""
     q = _check_quantization(quantization, w.tp_size)
     if q == "none" or w.quantization == q:
         return w
+    if w.quantization != "none":
+        raise ValueError(f"the weights are already quantised as {w.quantization}: load them again with "
+                         f"quantization={q} instead of quantising the rounded values a second time")
     attach_tiled(w)
     for L in w.layers:
         L.wqkv, L.wo, L.wgu, L.wd = (untile_weight(t) for t in (L.wqkv_t, L.wo_t, L.wgu_t, L.wd_t))
         _tile_layer(L, q)
-    w.lm_head_t, w.lm_head_q, w.lm_head_scale = _tile(untile_weight(w.lm_head_t), q)
+    w.lm_head_t, w.lm_head_q, w.lm_head_scale, w.lm_head_e = _tile(untile_weight(w.lm_head_t), q)
     w.quantization = q
     return w
 
@@ -193,6 +228,9 @@ def _kv_scale(t) -> float:
 
 def _check_quantization(quantization, tp_size: int) -> str:
     q = parse_quantization(quantization)
+    if q == "mxfp4" and tp_size > 1:
+        raise ValueError("quantization=mxfp4 is not supported with tensor parallelism (tp > 1): the block scales are "
+                         "not sharded; use --dp for more than one GPU")
     if q != "none" and tp_size > 1:
         raise ValueError("quantization=fp8 is not supported with tensor parallelism (tp > 1): the row scales are not "
                          "sharded; use --dp for more than one GPU")
@@ -201,7 +239,7 @@ def _check_quantization(quantization, tp_size: int) -> str:
 
 def convert_standard(cfg: MistralConfig, std, tp_rank: int = 0, tp_size: int = 1, device="cpu",
                      quantization=None) -> EngineWeights:
-    """Standard (HF-layout) weights -> this rank's engine weights (quantization="fp8": quantised once, here)."""
+    """Standard (HF-layout) weights -> this rank's engine weights (quantization="fp8" / "mxfp4": quantised once, here)."""
     quantization = _check_quantization(quantization, tp_size)
     cfg.validate(tp_size)
     D = cfg.head_dim

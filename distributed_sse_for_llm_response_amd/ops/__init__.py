@@ -191,6 +191,83 @@ def qkv_attention_decode_w8(x, w_q, w_scale, positions, slots, rope, q_out, k_ca
     return 0
 
 
+# ---- MXFP4 weights (W4A16; csrc/kernels/gemm_w4.hip): w_q = e2m1 nibble bytes [N, K / 2], w_e = e8m0 block scale
+# bytes [N, K / 32], both in the tiled layout (reference.py tile_weight_mxfp4).  1-64 rows on the GPU; each op mirrors
+# the bf16 op of the same name and equals it on the widened weight tile_weight(widen_weight_mxfp4(...)) up to fp32
+# summation order.
+W4_MAX_M = 64
+quantize_weight_mxfp4, widen_weight_mxfp4 = ref.quantize_weight_mxfp4, ref.widen_weight_mxfp4
+tile_weight_mxfp4, untile_weight_mxfp4 = ref.tile_weight_mxfp4, ref.untile_weight_mxfp4
+
+
+def gemm_out_w4(x, w_q, w_e, out):
+    """out[M, N] = x · widen(w_q, w_e)ᵀ (bf16 or fp32 out)."""
+    if _hip(x):
+        torch.ops.dsse.gemm_out_w4(x, w_q, w_e, out)
+    else:
+        ref.gemm_out_w4(x, w_q, w_e, out)
+
+
+def gemm_resid_w4(x, w_q, w_e, resid):
+    """resid[M, N] (fp32) += x · widen(w_q, w_e)ᵀ."""
+    if _hip(x):
+        torch.ops.dsse.gemm_resid_w4(x, w_q, w_e, resid)
+    else:
+        ref.gemm_resid_w4(x, w_q, w_e, resid)
+
+
+def gemm_silu_w4(x, w_q, w_e, out):
+    """gemm_silu over an MXFP4 weight (interleaved gate/up rows)."""
+    if _hip(x):
+        torch.ops.dsse.gemm_silu_w4(x, w_q, w_e, out)
+    else:
+        ref.gemm_silu_w4(x, w_q, w_e, out)
+
+
+def gemm_resid_split_w4(x, w_q, w_e, resid, part) -> int:
+    """gemm_resid_split over an MXFP4 weight: fp32 slabs [S, M, N] in `part` and S, or the sum in resid and 0."""
+    if _hip(x):
+        return int(torch.ops.dsse.gemm_resid_split_w4(x, w_q, w_e, resid, part))
+    ref.gemm_resid_w4(x, w_q, w_e, resid)
+    return 0
+
+
+def gemm_out_split_w4(x, w_q, w_e, out, part) -> int:
+    """gemm_out_split over an MXFP4 weight."""
+    if _hip(x):
+        return int(torch.ops.dsse.gemm_out_split_w4(x, w_q, w_e, out, part))
+    ref.gemm_out_w4(x, w_q, w_e, out)
+    return 0
+
+
+def gemm_qkv_rope_w4(x, w_q, w_e, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0,
+                     v_scale=1.0, scratch=None):
+    """gemm_qkv_rope over an MXFP4 weight (the unfused path of qkv_attention_decode_w4)."""
+    if _hip(x):
+        torch.ops.dsse.gemm_qkv_rope_w4(x, w_q, w_e, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv,
+                                        k_scale, v_scale, scratch)
+    else:
+        ref.gemm_qkv_rope_w4(x, w_q, w_e, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale,
+                             v_scale)
+
+
+def qkv_attention_decode_w4(x, w_q, w_e, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, slabs,
+                            block_tables, q_start, q_len, ctx_len, work_seq, work_tile, out, part_o, part_ml, part,
+                            nparts, k_scale=1.0, v_scale=1.0) -> int:
+    """qkv_attention_decode over an MXFP4 weight: the projection leaves fp32 slabs that the attention kernel
+    folds in unchanged (returns the slab count; 0 = gemm_qkv_rope_w4 + paged_attention ran instead)."""
+    if _hip(x):
+        return int(torch.ops.dsse.qkv_attention_decode_w4(x, w_q, w_e, positions, slots, rope, q_out, k_cache,
+                                                          v_cache, nh, nkv, slabs, block_tables, q_start, q_len,
+                                                          ctx_len, work_seq, work_tile, out, part_o, part_ml, part,
+                                                          nparts, k_scale, v_scale))
+    B = x.shape[0]
+    ref.gemm_qkv_rope_w4(x, w_q, w_e, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
+    ref.paged_attention(0, q_out.view(B, nh, 128), k_cache, v_cache, block_tables, q_start, q_len, ctx_len, work_seq,
+                        work_tile, out.view(B, nh, 128), part_o, part_ml, part, nparts, k_scale, v_scale)
+    return 0
+
+
 # ---- multi-LoRA (csrc/kernels/lora.hip): every row names its adapter slot in row_adapter (int32, -1 = none)
 LORA_RANKS = (8, 16, 32, 64)  # pool ranks the expand kernel is built for
 LORA_MAX_SLOTS = 8

@@ -215,6 +215,97 @@ def gemm_qkv_rope_w8(x, wq, ws, positions, slots, rope, q_out, k_cache, v_cache,
     gemm_qkv_rope(x, _widened_tiled(wq, ws), positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale, v_scale)
 
 
+# ---- MXFP4 weights (OCP e2m1 elements, one e8m0 scale per 32 consecutive K), W4A16: the one definition of what a
+# stored nibble and scale byte mean.  value = e2m1(nibble) * 2^(scale byte - 127).  Nibble code: bit 3 sign, bits 2-1
+# exponent, bit 0 mantissa, i.e. magnitudes FP4_GRID[code & 7]; a value that rounds to zero stores code 0, never 8.  The
+# byte at [n, k / 2] holds element k (even) in its low nibble and element k + 1 in its high nibble.  The block scale is
+# the smallest power of two s with 6 s >= amax(block), so the quotient never saturates and the ONE rounding is to the
+# e2m1 grid, to nearest with ties to the even code.  Every e2m1 value has two significant bits and a power of two only
+# moves the exponent, so widen_weight_mxfp4 is exact in bf16: the 4-bit kernels (v_cvt_scalef32_pk_bf16_fp4 in
+# registers) and the bf16 kernels over the widened copy multiply by identical weight values.
+FP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+FP4_MAX = 6.0
+MX_BLOCK = 32
+E8M0_BIAS, E8M0_MIN, E8M0_MAX = 127, 63, 191  # scale bytes are clamped to 2^-64 .. 2^64
+
+
+def quantize_weight_mxfp4(w: torch.Tensor):
+    """w [N, K] (K % 128 == 0, N % 16 == 0) -> (q uint8 [N, K / 2] row-major nibble pairs, e uint8 [N, K / 32])."""
+    N, K = w.shape
+    assert N % 16 == 0 and K % 128 == 0, (N, K)
+    blk = w.float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    _, ex = torch.frexp(amax / FP4_MAX)  # amax / 6 ~ m 2^ex with m in [0.5, 1): 2^ex is the scale unless m == 0.5
+    s = torch.ldexp(torch.ones_like(amax), ex)
+    # settle the candidate against amax itself (the quotient above is rounded); products with 2^ex are exact
+    s = torch.where(FP4_MAX * (s * 0.5) >= amax, s * 0.5, s)
+    s = torch.where(FP4_MAX * s < amax, s * 2.0, s)
+    _, es = torch.frexp(s)  # s = 0.5 * 2^es
+    e = (es - 1 + E8M0_BIAS).clamp(E8M0_MIN, E8M0_MAX)
+    e = torch.where(amax > 0, e, torch.full_like(e, E8M0_BIAS))
+    v = blk / torch.ldexp(torch.ones_like(amax), e - E8M0_BIAS)[:, :, None]
+    a = v.abs()
+    grid = torch.tensor(FP4_GRID, device=w.device)
+    mids = (grid[:-1] + grid[1:]) * 0.5
+    lo = torch.bucketize(a, mids, right=False)  # a value on a midpoint goes down ...
+    hi = torch.bucketize(a, mids, right=True)   # ... or up: take the even code of the two
+    code = torch.where((lo != hi) & (lo % 2 == 1), hi, lo)
+    code = torch.where((v < 0) & (code > 0), code + 8, code).to(torch.uint8).reshape(N, K)
+    return code[:, 0::2] | (code[:, 1::2] << 4), e.to(torch.uint8)
+
+
+def widen_weight_mxfp4(q: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """The bf16 weight the nibbles and scale bytes stand for (exact), row-major [N, K]."""
+    N, K = q.shape[0], q.shape[1] * 2
+    code = torch.stack((q & 15, q >> 4), dim=2).reshape(N, K).long()
+    mag = torch.tensor(FP4_GRID, device=q.device)[code & 7]
+    val = torch.where(code >= 8, -mag, mag).reshape(N, K // MX_BLOCK, MX_BLOCK)
+    s = torch.ldexp(torch.ones(e.shape, device=q.device), e.int() - E8M0_BIAS)
+    return (val * s[:, :, None]).reshape(N, K).to(torch.bfloat16)
+
+
+def tile_weight_mxfp4(q: torch.Tensor, e: torch.Tensor):
+    """Row-major (q [N, K / 2], e [N, K / 32]) -> the device layout (csrc/kernels/api.h kTileChunkF4 / kTileScaleF4):
+    two tensors of the same shapes and dtype, permuted storage, over the (16-row tile T, 128-column chunk c) blocks of
+    tile_weight, block-major (T, c).  Nibbles, 1 KiB per block: [lane = r + 16 g][16 bytes] = the bytes of
+    W[16T + r][128c + 32g .. 32g + 31], one MX block.  Scales, 64 B per block: byte [lane] = that block's scale."""
+    N, K = q.shape[0], q.shape[1] * 2
+    assert N % 16 == 0 and K % 128 == 0 and e.shape == (N, K // MX_BLOCK), (q.shape, e.shape)
+    qt = q.reshape(N // 16, 16, K // 128, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(N, K // 2)
+    et = e.reshape(N // 16, 16, K // 128, 4).permute(0, 2, 3, 1).contiguous().view(N, K // MX_BLOCK)
+    return qt, et
+
+
+def untile_weight_mxfp4(qt: torch.Tensor, et: torch.Tensor):
+    """Inverse of :func:`tile_weight_mxfp4`."""
+    N, K = qt.shape[0], qt.shape[1] * 2
+    q = qt.reshape(N // 16, K // 128, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(N, K // 2)
+    e = et.reshape(N // 16, K // 128, 4, 16).permute(0, 3, 1, 2).reshape(N, K // MX_BLOCK)
+    return q.contiguous(), e.contiguous()
+
+
+def _widened_tiled_f4(wq, we):
+    """The tiled bf16 weight of tiled MXFP4 nibbles + scale bytes: what the bf16 reference GEMMs take."""
+    return tile_weight(widen_weight_mxfp4(*untile_weight_mxfp4(wq, we)))
+
+
+def gemm_out_w4(x, wq, we, out):
+    gemm_out(x, _widened_tiled_f4(wq, we), out)
+
+
+def gemm_resid_w4(x, wq, we, resid):
+    gemm_resid(x, _widened_tiled_f4(wq, we), resid)
+
+
+def gemm_silu_w4(x, wq, we, out):
+    gemm_silu(x, _widened_tiled_f4(wq, we), out)
+
+
+def gemm_qkv_rope_w4(x, wq, we, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
+    gemm_qkv_rope(x, _widened_tiled_f4(wq, we), positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale,
+                  v_scale)
+
+
 def rope_kv_write(qkv, positions, slots, rope, q_out, k_cache, v_cache, nh, nkv, k_scale=1.0, v_scale=1.0):
     T = qkv.shape[0]
     u = _unpermute_units(qkv.float(), nh + 2 * nkv)

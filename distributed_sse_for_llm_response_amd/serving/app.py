@@ -71,7 +71,8 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
                                       quantization=quant)
         pool = lora_pool(mcfg, device)  # resident before the page budget below is sized, so its bytes are counted
         # the page budget below is what is free once the weights are resident: under quantization both copies (the
-        # widened bf16 one, 14.5 GB for Mistral-7B, and the FP8 one, 7.2 GB) are already allocated here
+        # widened bf16 one, 14.5 GB for Mistral-7B, and the FP8 one, 7.2 GB, or the MXFP4 one, 3.8 GB) are already
+        # allocated here
         free, total = torch.cuda.mem_get_info(device)
         budget = int(total * cfg.gpu_memory_utilization) - (total - free) - (2 << 30)
         nkv = mcfg.num_kv_heads // tp
@@ -82,10 +83,12 @@ def build_engine(cfg: ServeConfig, device=None, comm=None):
         runner.capture()
     kv = runner.kv
     if comm is None or comm.rank == 0:
-        f8 = w.nbytes_fp8()
-        print(f"[engine] weights: quantization {runner.quantization}, bf16 copy {(w.nbytes() - f8) / 1e9:.2f} GB"
+        f8, f4 = w.nbytes_fp8(), w.nbytes_fp4()
+        print(f"[engine] weights: quantization {runner.quantization}, bf16 copy {(w.nbytes() - f8 - f4) / 1e9:.2f} GB"
               + (f" (widened from fp8), fp8 copy {f8 / 1e9:.2f} GB (decode buckets of 64 rows or fewer)"
-                 if f8 else ""), flush=True)
+                 if f8 else "")
+              + (f" (widened from mxfp4), mxfp4 copy {f4 / 1e9:.2f} GB (decode buckets of 64 rows or fewer)"
+                 if f4 else ""), flush=True)
         print(f"[engine] KV cache: {'fp8_e4m3' if kv.is_fp8 else 'bf16'} ({cfg.kv_cache_dtype}), "
               f"{KVCache.bytes_per_block(kv.num_layers, kv.nkv, kv.dtype) // 32 // 1024} KiB per token"
               f"{' per rank' if comm is not None and comm.size > 1 else ''}, {kv.num_blocks} pages of 32 tokens",

@@ -12,7 +12,8 @@ Engine keys (new): TP, DP, DP_PREFIX, DP_WORKER_TIMEOUT_MS, MAX_MODEL_LEN, MAX_B
   SEED, MAX_TOKENS, PREFILL_BUDGET, TOKENIZER_PATH, WEIGHTS_PATH, ENABLE_PREFIX_CACHING (default 0),
   DP_PREFIX_AFFINITY_SLACK (default 4, unmeasured), KV_CACHE_DTYPE (auto | bf16 | fp8 | fp8_e4m3; default auto = bf16),
   KV_OFFLOAD_GB (GiB of pinned host memory per engine process behind the prefix cache; default 0 = off),
-  QUANTIZATION (none | fp8; default none; fp8 = FP8 e4m3 weights for decode buckets of 64 rows or fewer, TP = 1),
+  QUANTIZATION (none | fp8 | mxfp4; default none; fp8 = FP8 e4m3 weights, mxfp4 = OCP MXFP4 weights, either for decode
+  buckets of 64 rows or fewer, TP = 1),
   ENABLE_LORA (default 0), LORA_MODULES (comma-separated NAME=PATH of PEFT directories), MAX_LORAS (slots, default 4,
   at most 8), MAX_LORA_RANK (8 | 16 | 32 | 64, default 16); TP = 1 and bf16 weights only.
 """
@@ -36,7 +37,7 @@ def parse_kv_cache_dtype(v) -> str:
 
 
 # weight quantisation at load (engine/weights.py keeps its own copy of the list: no torch import at parse time)
-QUANTIZATIONS = ("none", "fp8")
+QUANTIZATIONS = ("none", "fp8", "mxfp4")
 
 
 def parse_quantization(v) -> str:
@@ -131,8 +132,9 @@ class ServeConfig:
     # host tier of the prefix cache: GiB of pinned host memory per engine process that keep evicted KV pages (0 = off;
     # needs enable_prefix_caching, not available with tp > 1); passed to every engine replica
     kv_offload_gb: float = 0.0
-    # weight quantisation at load: none, or fp8 = W8A16 e4m3 weights for decode buckets of 64 rows or fewer beside a
-    # widened bf16 copy for everything else (not available with tp > 1); passed to every engine replica
+    # weight quantisation at load: none, fp8 = W8A16 e4m3 weights or mxfp4 = W4A16 OCP MXFP4 weights (e2m1 elements,
+    # one e8m0 scale per 32 K), either for decode buckets of 64 rows or fewer beside a widened bf16 copy for everything
+    # else (not available with tp > 1); passed to every engine replica
     quantization: str = "none"
     # LoRA serving (engine/lora.py): every NAME=PATH of lora_modules (comma-separated) is loaded into one of max_loras
     # pool slots of rank max_lora_rank at start-up; "model": NAME of a chat request then selects it.  TP = 1, bf16
@@ -236,8 +238,9 @@ class ServeConfig:
                                  "own host tier), or set it to 0")
         if parse_quantization(self.quantization) != "none" and self.tp > 1:
             raise ValueError(f"--quantization {self.quantization} / QUANTIZATION is not supported with tensor "
-                             f"parallelism (tp = {self.tp}): the row scales are not sharded; run with --tp 1 (data "
-                             "parallelism, --dp N, works), or set it to none")
+                             f"parallelism (tp = {self.tp}): the {'block' if self.quantization == 'mxfp4' else 'row'} "
+                             "scales are not sharded; run with --tp 1 (data parallelism, --dp N, works), or set it "
+                             "to none")
         mods = parse_lora_modules(self.lora_modules)
         if mods and not self.enable_lora:
             raise ValueError("--lora-modules / LORA_MODULES needs --enable-lora (ENABLE_LORA=1)")
@@ -247,7 +250,8 @@ class ServeConfig:
                                  "the adapters are not sharded; run with --tp 1 (data parallelism, --dp N, works)")
             if parse_quantization(self.quantization) != "none":
                 raise ValueError(f"--enable-lora / ENABLE_LORA is not supported with --quantization "
-                                 f"{self.quantization}: the FP8 decode kernels cannot take a delta; set it to none")
+                                 f"{self.quantization}: the {'MXFP4' if self.quantization == 'mxfp4' else 'FP8'} decode kernels "
+                                 "cannot take a delta; set it to none")
             if not 1 <= int(self.max_loras) <= LORA_MAX_SLOTS:
                 raise ValueError(f"--max-loras / MAX_LORAS must be in [1, {LORA_MAX_SLOTS}], got {self.max_loras}")
             if int(self.max_lora_rank) not in LORA_RANKS:

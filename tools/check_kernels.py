@@ -95,6 +95,65 @@ def check_w8(dev):
         ops.refresh_env()
 
 
+def check_w4(dev):
+    """The MXFP4-weight GEMMs (gemm_w4.hip): every epilogue over the row counts and K ranges of tests/test_w4_gpu.py must
+    record nothing; a KV slot past the cache in the unfused QKV epilogue must be caught in that file."""
+    from distributed_sse_for_llm_response_amd.ops import reference as R
+
+    g = torch.Generator().manual_seed(4)
+    i32 = dict(dtype=torch.int32, device=dev)
+    nh, nkv = 8, 2
+    ops.kernel_checks()  # clear
+    for K in (1536, 4096):
+        ws = {}
+        for N in (512, 1024, 2 * 704, (nh + 2 * nkv) * 128):
+            q, e = R.quantize_weight_mxfp4((torch.randn(N, K, generator=g) / math.sqrt(K)).bfloat16())
+            ws[N] = tuple(t.to(dev) for t in R.tile_weight_mxfp4(q, e))
+        for M in (1, 16, 17, 33, 64):
+            x = torch.randn(M, K, generator=g).bfloat16().to(dev)
+            part = torch.zeros(8 * M * 1536, device=dev)
+            for dt in (torch.float32, torch.bfloat16):
+                ops.gemm_out_w4(x, *ws[512], torch.zeros(M, 512, device=dev, dtype=dt))
+            resid = torch.zeros(M, 1024, device=dev)
+            ns = ops.gemm_resid_split_w4(x, *ws[1024], resid, part)
+            ops.rmsnorm(resid, torch.ones(1024, dtype=torch.bfloat16, device=dev),
+                        torch.zeros(M, 1024, dtype=torch.bfloat16, device=dev), 1e-5, part=part, nsplit=ns)
+            ops.gemm_resid_w4(x, *ws[1024], resid)
+            ops.gemm_silu_w4(x, *ws[2 * 704], torch.zeros(M, 704, dtype=torch.bfloat16, device=dev))
+            kc = torch.zeros(2 * M, nkv, 32, 128, dtype=torch.bfloat16, device=dev)
+            vc = torch.zeros(2 * M, nkv, 128, 32, dtype=torch.bfloat16, device=dev)
+            ar = torch.arange(M, **i32)
+            pos = (ar * 7) % 60
+            bt = torch.arange(2 * M, **i32).view(M, 2)
+            slots = bt[ar.long(), (pos // 32).long()] * 32 + pos % 32
+            rope = torch.zeros(64, 64, 2, device=dev)
+            qo, out = (torch.zeros(M, nh * 128, dtype=torch.bfloat16, device=dev) for _ in range(2))
+            po, pml = torch.zeros(M * nkv * 16 * 128, device=dev), torch.zeros(M * nkv * 16 * 2, device=dev)
+            ops.qkv_attention_decode_w4(x, *ws[1536], pos, slots, rope, qo, kc, vc, nh, nkv, part, bt, ar,
+                                        torch.ones(M, **i32), pos + 1, ar, torch.zeros(M, **i32), out, po, pml, 128, 1)
+            ops.gemm_qkv_rope_w4(x, *ws[1536], pos, slots, rope, qo, kc, vc, nh, nkv)
+    clean = ops.kernel_checks(raise_on_error=False)
+    if clean:
+        raise SystemExit(f"false positive on valid MXFP4-weight GEMM launches: {clean}")
+    print("gemm_w4.hip: clean over the epilogue shapes")
+    bad_slots = slots.clone()
+    bad_slots[0] = 2 * M * 32 + 5
+    # unsplit, so that the kernel's own epilogue sees the slot (the split-K reduction is a template shared by the GEMM
+    # files: which file's copy runs, and records, is the linker's choice)
+    saved = os.environ.get("DSSE_KERNEL_CFG")
+    os.environ["DSSE_KERNEL_CFG"] = ops.kernel_cfg_env(w4_split=1)
+    ops.refresh_env()
+    try:
+        expect(lambda: ops.gemm_qkv_rope_w4(x, *ws[1536], pos, bad_slots, rope, qo, kc, vc, nh, nkv), "gemm_w4.hip",
+               "MXFP4 QKV epilogue: slot past the cache")
+    finally:
+        if saved is None:
+            del os.environ["DSSE_KERNEL_CFG"]
+        else:
+            os.environ["DSSE_KERNEL_CFG"] = saved
+        ops.refresh_env()
+
+
 def check_lora(dev):
     """The multi-LoRA products (lora.hip): the row counts and ranks of tests/test_lora_gpu.py must record nothing; an
     adapter slot past the pool must be caught in that file (the row is then treated as having no adapter)."""
@@ -134,6 +193,11 @@ def main():
         print("CHECKS-OK")
         return
 
+    if sys.argv[1:] == ["--only", "w4"]:
+        check_w4(dev)
+        torch.cuda.synchronize()
+        print("CHECKS-OK")
+        return
     if sys.argv[1:] == ["--only", "lora"]:
         check_lora(dev)
         torch.cuda.synchronize()
@@ -203,6 +267,7 @@ def main():
                                    torch.zeros(1, **i32), nblk), "elementwise.hip", "decode_prep: bad page id")
     check_w8(dev)
     check_lora(dev)
+    check_w4(dev)
     torch.cuda.synchronize()
     print("CHECKS-OK")
 
